@@ -12,9 +12,15 @@ collective; RCCL only reduces the counters.  ``--gpus N`` without a launcher
 
 Prints ONE JSON line (rank 0), with the roofline of the solve kernel against HBM
 (algorithmic bytes per SURVEY.md §8(d): 2*257*W*N bytes per instance-iteration
-plus (13N+31)*W bytes of per-solve I/O) and the CPU baseline (rank 0, N = 1 only):
-the scalar C++ fp64 build of the same interior-point solver (mr_solver.h
-``Solver``, OpenMP over instances) on a time-bounded sample of the same shard.
+plus (13N+31)*W bytes of per-solve I/O), all from the timed steps.
+
+A plain run does only that: set up, warm up, time ``--steps`` solves, write the last
+step's outputs if ``--dump-outputs DIR`` is given, print the line.  ``--full`` adds
+the figures that take runs of their own: the B = 1 latency, the agent's call, the
+pipelined (serving-mode) figure, the spread over the 8 shards, the measured copy
+bandwidth of the roofline, and the CPU baseline (rank 0, N = 1 only): the scalar
+C++ fp64 build of the same interior-point solver (mr_solver.h ``Solver``, OpenMP
+over instances) on a time-bounded sample of the same shard.
 """
 import argparse
 import hashlib
@@ -338,6 +344,29 @@ def shard_spread(args, solver, out, dev, stream, ms0):
                     "(shard 0: the timed steps' p50); the 8-GPU job's batch time is the slowest shard's"}
 
 
+DUMP_MAX_BYTES = 64 * 10**6 - (1 << 16)  # 64 MB on disk, the .npy headers included
+
+
+def dump_outputs(path, out, seed=0):
+    """--dump-outputs: what the timed path's last step left in its output tensors (the arrays a caller of
+    BatchSolver.launch receives: X, U, S, eC, eL, status, iters, obj, kkt, constr_viol), one
+    ``<name>.npy`` each, float64 (the integer status / iters converted), instances on the last axis.
+    Above 64 MB in all, the same fixed sample of instances (seeded, ascending) of every array."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B = int(out["status"].shape[0])
+    per_instance = sum(8 * (v.numel() // B) for v in out.values())
+    keep = min(B, DUMP_MAX_BYTES // per_instance)
+    idx = None
+    if keep < B:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(B, keep, replace=False)))
+    for k, v in out.items():
+        a = v.cpu()
+        if idx is not None:
+            a = a.index_select(a.dim() - 1, idx)
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a.numpy().astype(np.float64)))
+
+
 def cpu_check(args, rank, world):
     """--cpu-check: the multi-rank plumbing without a GPU (gloo): each rank builds its shard and the
     counters go through reduce_counters; rank 0 prints the shard layout.  Used by tests/test_multirank.py."""
@@ -371,10 +400,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C4")
     ap.add_argument("--per-gpu", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not part of the line's value: B = 1 latency, the agent's call, the "
+                         "pipelined figure, the shard spread, the copy bandwidth and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output arrays (rank 0) to DIR/<name>.npy")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the B = 1 latency probe and the pipelined figure (profiling runs: "
-                                                           "only the timed launches)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the B = 1 latency probe, the agent's call, the "
+                                                           "pipelined figure and the shard spread")
     ap.add_argument("--cpu-check", action="store_true", help="multi-rank plumbing on CPU (gloo), no solve")
     ap.add_argument("--dispatch-order", type=int, default=1, help="mr_config.dispatch_order (A/B runs)")
     ap.add_argument("--pipeline", type=int, default=4,
@@ -403,6 +437,8 @@ def main():
     # on CPU in tests/test_multirank.py
     backend = os.environ.get("MR_BENCH_BACKEND", "nccl")
     dry = args.dry_run
+    if dry and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs the solves (--dry-run skips them)")
     if dry and backend != "gloo":
         raise SystemExit("--dry-run needs MR_BENCH_BACKEND=gloo (it is the CPU test of the rank plumbing)")
     # MR_BENCH_PG=1: the process group and its collectives also at world size 1 -- the multi-GPU path's RCCL
@@ -462,12 +498,15 @@ def main():
         kms = [starts[s].elapsed_time(ends[s]) for s in range(args.steps)]
         it = out["iters"].cpu().numpy()
         stc = np.bincount(out["status"].cpu().numpy(), minlength=5)[:5]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out)
     iters_launch = float(it.sum())            # one launch (every launch solves the same shard)
     alg_bytes = algorithmic_bytes(cfg["N"], W, it)
 
     # B = 1 latency (same configuration, first instance), p50 of 5 runs
     lat_b1_ms = None
-    if not args.no_latency and not dry:
+    extras = args.full and not args.no_latency and not dry
+    if extras:
         b1 = {k: (v[..., :1].copy() if v is not None else None) for k, v in batch.items()}
         s1 = solver_for_config(args.config, 1, device=local)
         d1 = s1.to_device(b1)
@@ -482,15 +521,15 @@ def main():
         lat_b1_ms = float(np.median(lat[1:]) * 1e3)
 
     agent = None
-    if not args.no_latency and not dry and rank == 0:
+    if extras and rank == 0:
         agent = agent_call_gpu(local)
 
     pipe = None
-    if args.pipeline >= 2 and world == 1 and not dry and not args.no_latency:
+    if args.pipeline >= 2 and world == 1 and extras:
         pipe = pipelined(args, solver, dev_in, out, batch, B, dev, local, args.pipeline)
 
     spread = None
-    if world == 1 and not dry and not args.no_latency:
+    if world == 1 and extras:
         spread = shard_spread(args, solver, out, dev, stream, float(np.median(kms)))
 
     tot, elapsed_max = reduce_counters(
@@ -498,7 +537,7 @@ def main():
         elapsed, world, pg)
 
     copy_gbs = None
-    if rank == 0 and not dry:
+    if args.full and rank == 0 and not dry:
         copy_gbs = copy_bandwidth(dev)
 
     if rank == 0:
@@ -551,8 +590,8 @@ def main():
                                    "throughput is `value`)") if world > 1 else "the single GPU's launch",
                          "copy_gbs": copy_gbs,
                          "frac_vs_copy": (achieved / copy_gbs) if copy_gbs else None,
-                         "copy_source": "measured in this run: 1 GiB fp32 device-to-device copy (torch copy_, "
-                                        "read + write bytes), HIP events",
+                         "copy_source": ("measured in this run: 1 GiB fp32 device-to-device copy (torch copy_, "
+                                         "read + write bytes), HIP events") if copy_gbs else None,
                          "compute": compute},
         }
         if pipe is not None:
@@ -569,7 +608,7 @@ def main():
             line["process_group"] = {"backend": dist.get_backend(), "world_size": world,
                                      "collectives": "barrier around the timed steps; all_reduce SUM of the counters, "
                                                     "MAX of the wall clock"}
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             line["cpu_baseline"] = cpu_baseline(args.config, batch, it, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if pg:

@@ -31,7 +31,7 @@ step pmc_sq 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VAL
 step pmc_sum 120 python mpc-racing_amd/tools/pmc_summary.py gpurun_out/prof/run_kernel_stats.csv gpurun_out/pmc_fetch/run_counter_collection.csv gpurun_out/pmc_write/run_counter_collection.csv gpurun_out/pmc_C4.json mr_wave_kernel $B C4 gpurun_out/pmc_sq/run_counter_collection.csv
 # the bench line's roofline.traffic comes from profiles/pmc_C4.json when its library hash is this build's
 [ -s gpurun_out/pmc_C4.json ] && cp gpurun_out/pmc_C4.json profiles/pmc_C4.json
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 if [ -x variants/pmc_calib ]; then
   step calib_fetch 120 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/calib_fetch -o run --output-format csv -- variants/pmc_calib
   step calib_write 120 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/calib_write -o run --output-format csv -- variants/pmc_calib
@@ -40,7 +40,7 @@ step timeline 300 python -u mpc-racing_amd/tools/timeline_probe.py C4 1
 fi
 if [[ $PART == *B* ]]; then
 for c in C2 C3 C5; do
-  step bench_$c 600 python bench.py --config $c --no-cpu-baseline
+  step bench_$c 600 python bench.py --config $c --full --no-cpu-baseline
 done
 # kernel statistics and HBM traffic of C2, C3 and C5 (same passes as C4's; C5 also the SQ pass)
 for c in C2 C3 C5; do
