@@ -35,8 +35,8 @@ extern "C" {
 /* ABI version (mr_version()): bumped whenever a struct layout or an entry point's meaning changes, so
    a caller built against another header can refuse to run (101: mr_config.dispatch_order,
    mr_outputs.lam_g / timeline, mr_config without lane_penalty (hard lane rows), status 4 = infeasible;
-   102: mr_inputs.order_hint, dispatch_order 2) */
-#define MR_ABI_VERSION 102
+   102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit) */
+#define MR_ABI_VERSION 103
 
 #define MR_OK 0
 #define MR_ERR_ARG (-1)
@@ -252,6 +252,56 @@ int mr_agent_sense(const mr_track* tr, int32_t n, const double* X, const double*
    Runs on the device that owns `state` (MR_ERR_ARG if it is not a HIP device pointer). */
 int mr_plant_step(int32_t model, int32_t n, const double* state, const double* cmd, double dt, double* out,
                   void* hip_stream);
+
+/* ---- tyre-model fitting (learning/train.py:78-192 driving learning/vehicle.py:136-205) ---------------
+ * Fits the lateral tyre law of the reference's one-step torch vehicle model to logged rows by minibatch
+ * gradient descent: minibatches of 64 rows (train.py BATCH_SIZE), one 64-lane wavefront per training
+ * run, all epochs in one launch (csrc/mr_tyrefit.h).  Rows are structure-of-arrays [15][n]:
+ * X, Y, yaw, vx, vy, yawdot, throttle, steer, dt, then the six next-state targets (train.py:32-37
+ * FEATURES + TARGETS).  Parameters per set / run: linear [2] = front, back stiffness; Pacejka [18] =
+ * a[0..8] front, a[0..8] back, with the vertical loads Fz [2] = front, back beside them.  The loss is
+ * torch's nn.MSELoss(): the mean over rows x 6 of (prediction - target)^2; gradients are analytic in
+ * the cancellation-free form.  All arrays are caller-owned DEVICE pointers; results are bitwise
+ * repeatable and do not depend on how many sets / runs share a launch. */
+#define MR_TYRE_LINEAR 0  /* Fy = stiffness * alpha (learning/vehicle.py:61-67)  */
+#define MR_TYRE_PACEJKA 1 /* magic formula, a[0..8] (learning/vehicle.py:70-92)  */
+#define MR_OPT_SGD 0      /* torch.optim.SGD                                      */
+#define MR_OPT_ADAM 1     /* torch.optim.Adam (train.py's default)                */
+#define MR_OPT_ADAMW 2    /* torch.optim.AdamW (decoupled weight decay)           */
+
+typedef struct mr_tyrefit_config {
+  int32_t kind;      /* MR_TYRE_* */
+  int32_t optimizer; /* MR_OPT_*  */
+  int32_t epochs;    /* train.py EPOCHS = 25 */
+  int32_t patience;  /* ReduceLROnPlateau patience (train.py PATIENCE = 2) */
+  double factor;     /* ReduceLROnPlateau factor (train.py FACTOR = 1/2)   */
+  /* VehicleParameters (models/VehicleParameters.py:3-41) read by Vehicle.forward */
+  double m, Iz, lf, lr, T_max, r_wheel, C_wheel, R, rho, C_d, A_f, C_roll, g, max_steer_deg;
+} mr_tyrefit_config;
+
+int mr_tyrefit_config_default(mr_tyrefit_config* cfg);
+/* loss [P] and grad [P][n_par] of P parameter sets params [P][n_par], Fz [P][2] over rows [15][n].
+   One wavefront per (set, chunk of 64 rows); the chunks' partial sums are added in chunk order by a second
+   kernel.  The call owns the partials buffer and synchronises the stream before it returns. */
+int mr_tyre_loss_grad(const mr_tyrefit_config* cfg, int32_t n, const double* rows, int32_t P, const double* params,
+                      const double* Fz, double* loss, double* grad, void* hip_stream);
+/* R independent training runs over train [15][n_train], validated each epoch on val [15][n_val].
+   init [R][n_par], Fz [R][2], hyper [R][5] = lr, beta1, beta2, eps, weight_decay (torch's meanings; SGD
+   reads lr and weight_decay).  perm: int32 [epochs][n_train], row order of every epoch (minibatch b of
+   epoch e is perm[e][64 b .. 64 b + 63], the last one partial); shared by all runs when
+   perm_stride_run == 0, else run r reads perm + r * perm_stride_run.  Entries are checked on the device
+   before the fit starts (MR_ERR_ARG if any is outside [0, n_train); the call synchronises the stream for
+   that).  End of epoch: the validation loss is the mean over minibatches of 64 of each batch's MSE, then
+   ReduceLROnPlateau(mode min, factor, patience, relative threshold 1e-4, cooldown 0, eps 1e-8).
+   Outputs: p_final, p_best [R][n_par] (parameters at the lowest validation loss), train_loss, val_loss,
+   lr_hist [R][epochs] (lr after the scheduler's step), flag [R] = 1 when a non-finite value appeared:
+   that run stopped updating, kept its last finite parameters, and its unfinished epochs are NaN.
+   p_steps: optional [R][epochs * ceil(n_train / 64)][n_par], the parameters after every optimiser step
+   (NaN for steps a stopped run never took); NULL to skip. */
+int mr_tyre_fit(const mr_tyrefit_config* cfg, int32_t n_train, const double* train, int32_t n_val, const double* val,
+                int32_t R, const double* init, const double* Fz, const double* hyper, const int32_t* perm,
+                int64_t perm_stride_run, double* p_final, double* p_best, double* train_loss, double* val_loss,
+                double* lr_hist, int32_t* flag, double* p_steps, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #include "mr_track.h"
 #include "mr_agent.h"
 #include "mr_plant.h"
+#include "mr_tyrefit.h"
 #include <vector>
 
 using namespace mr;
@@ -476,6 +477,42 @@ __global__ __launch_bounds__(kTrackBlock) void mr_plant_step_kernel(int model, i
   for (int j = 0; j < 6; ++j) out[(int64_t)j * n + i] = o[j];
 }
 
+// Tyre-model fitting (mr_tyrefit.h).  Loss / gradient: one wavefront per (parameter set, chunk of 64
+// rows) reduces its chunk into the partials buffer; a second kernel adds the partials in chunk order
+// (no atomics: the result does not depend on P or on scheduling).
+__global__ __launch_bounds__(64) void tyre_loss_grad_kernel(mr_tyrefit_config cfg, int n, const double* rows,
+                                                            int n_chunk, const double* params, const double* Fz,
+                                                            double* partials) {
+  Wv w{(int)threadIdx.x};
+  tf_lossgrad_chunk(w, cfg, n, rows, (int)(blockIdx.x / n_chunk), (int)(blockIdx.x % n_chunk), n_chunk, params, Fz,
+                    partials);
+}
+__global__ __launch_bounds__(64) void tyre_loss_grad_finish_kernel(mr_tyrefit_config cfg, int n, int P, int n_chunk,
+                                                                   const double* partials, const double* params,
+                                                                   const double* Fz, double* loss, double* grad) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= P) return;
+  tf_lossgrad_finish(cfg, n, p, n_chunk, partials, params, Fz, loss, grad);
+}
+// checking pass of mr_tyre_fit: *bad = 1 when any perm entry is outside [0, n_train) (every writer
+// stores the same value)
+__global__ __launch_bounds__(256) void tyre_perm_check_kernel(const int32_t* perm, int64_t per_run, int R_perm,
+                                                              int64_t stride, int n_train, int* bad) {
+  const int64_t total = per_run * R_perm;
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < total; k += (int64_t)gridDim.x * 256) {
+    const int32_t v = perm[(k / per_run) * stride + (k % per_run)];
+    if (v < 0 || v >= n_train) *bad = 1;
+  }
+}
+// One 64-lane wavefront per training run, persistent over all epochs: the run is a serial chain of
+// small steps (gather 64 rows, evaluate, 9 butterfly reductions, redundant optimiser update);
+// independent runs fill the machine.  The dataset (<= 770 KB for the reference's largest) stays in L2.
+template <int KIND>
+__global__ __launch_bounds__(64) void tyre_fit_kernel(TfFitArgs A) {
+  Wv w{(int)threadIdx.x};
+  tf_fit_run<KIND>(A, (int)blockIdx.x, w);
+}
+
 extern "C" {
 
 int mr_version(void) { return MR_ABI_VERSION; }
@@ -757,6 +794,86 @@ int mr_plant_step(int32_t model, int32_t n, const double* state, const double* c
   MR_GUARD_DEVICE(dev);  // the arrays' device, not whichever device is current
   hipLaunchKernelGGL(mr_plant_step_kernel, dim3((n + kTrackBlock - 1) / kTrackBlock), dim3(kTrackBlock), 0,
                      (hipStream_t)hip_stream, (int)model, (int)n, state, cmd, dt, out);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_tyrefit_config_default(mr_tyrefit_config* cfg) {
+  if (!cfg) return fail(MR_ERR_ARG, "null config");
+  fill_default_tyrefit_config(cfg);
+  return MR_OK;
+}
+
+int mr_tyre_loss_grad(const mr_tyrefit_config* cfg, int32_t n, const double* rows, int32_t P, const double* params,
+                      const double* Fz, double* loss, double* grad, void* hip_stream) {
+  if (const char* e = tyrefit_check_config(cfg)) return fail(MR_ERR_ARG, e);
+  if (!rows || !params || !Fz || !loss || !grad) return fail(MR_ERR_ARG, "null argument");
+  if (n < 1) return fail(MR_ERR_ARG, "n < 1");
+  if (P < 1) return fail(MR_ERR_ARG, "P < 1");
+  if (n > 0x7fffffff / TF_COLS) return fail(MR_ERR_ARG, "too many rows");
+  const int n_chunk = (n + WL - 1) / WL;
+  if ((int64_t)P * n_chunk > 0x7fffffff) return fail(MR_ERR_ARG, "P * ceil(n / 64) exceeds the grid limit");
+  int dev = -1;
+  if (pointer_device(rows, &dev) != 0) return fail(MR_ERR_ARG, "rows is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  hipStream_t st = (hipStream_t)hip_stream;
+  double* partials = nullptr;
+  HIP_TRY(hipMalloc(&partials, sizeof(double) * TF_NSUM * (size_t)P * n_chunk));
+  hipLaunchKernelGGL(tyre_loss_grad_kernel, dim3((unsigned)(P * n_chunk)), dim3(64), 0, st, *cfg, (int)n, rows, n_chunk,
+                     params, Fz, partials);
+  hipLaunchKernelGGL(tyre_loss_grad_finish_kernel, dim3((P + 63) / 64), dim3(64), 0, st, *cfg, (int)n, (int)P, n_chunk,
+                     (const double*)partials, params, Fz, loss, grad);
+  hipError_t e1 = hipGetLastError();
+  hipError_t e2 = hipStreamSynchronize(st);  // the partials buffer is released below
+  (void)hipFree(partials);
+  HIP_TRY(e1);
+  HIP_TRY(e2);
+  return MR_OK;
+}
+
+int mr_tyre_fit(const mr_tyrefit_config* cfg, int32_t n_train, const double* train, int32_t n_val, const double* val,
+                int32_t R, const double* init, const double* Fz, const double* hyper, const int32_t* perm,
+                int64_t perm_stride_run, double* p_final, double* p_best, double* train_loss, double* val_loss,
+                double* lr_hist, int32_t* flag, double* p_steps, void* hip_stream) {
+  if (const char* e = tyrefit_check_fit(cfg, n_train, n_val, R, perm_stride_run)) return fail(MR_ERR_ARG, e);
+  if (!train || !val || !init || !Fz || !hyper || !perm || !p_final || !p_best || !train_loss || !val_loss ||
+      !lr_hist || !flag)
+    return fail(MR_ERR_ARG, "null argument");
+  int dev = -1;
+  if (pointer_device(train, &dev) != 0) return fail(MR_ERR_ARG, "train is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  hipStream_t st = (hipStream_t)hip_stream;
+  // checking pass: no perm entry is dereferenced as a row index before it is known to be in range
+  int* bad_dev = nullptr;
+  int bad = 0;
+  HIP_TRY(hipMalloc(&bad_dev, sizeof(int)));
+  hipError_t e0 = hipMemsetAsync(bad_dev, 0, sizeof(int), st);
+  const int64_t per_run = (int64_t)cfg->epochs * n_train;
+  const int R_perm = perm_stride_run ? R : 1;
+  const int64_t blocks = (per_run * R_perm + 255) / 256;
+  hipLaunchKernelGGL(tyre_perm_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, perm,
+                     per_run, R_perm, perm_stride_run, (int)n_train, bad_dev);
+  hipError_t e1 = hipGetLastError();
+  hipError_t e2 = hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, st);
+  hipError_t e3 = hipStreamSynchronize(st);
+  (void)hipFree(bad_dev);
+  HIP_TRY(e0);
+  HIP_TRY(e1);
+  HIP_TRY(e2);
+  HIP_TRY(e3);
+  if (bad) return fail(MR_ERR_ARG, "perm entry out of range [0, n_train)");
+  TfFitArgs A;
+  A.cfg = *cfg;
+  A.n_train = n_train; A.n_val = n_val; A.R = R;
+  A.train = train; A.val = val; A.init = init; A.Fz = Fz; A.hyper = hyper;
+  A.perm = perm; A.perm_stride_run = perm_stride_run;
+  A.p_final = p_final; A.p_best = p_best; A.train_loss = train_loss; A.val_loss = val_loss; A.lr_hist = lr_hist;
+  A.flag = flag;
+  A.p_steps = p_steps;
+  if (cfg->kind == MR_TYRE_PACEJKA)
+    hipLaunchKernelGGL(tyre_fit_kernel<MR_TYRE_PACEJKA>, dim3((unsigned)R), dim3(64), 0, st, A);
+  else
+    hipLaunchKernelGGL(tyre_fit_kernel<MR_TYRE_LINEAR>, dim3((unsigned)R), dim3(64), 0, st, A);
   HIP_TRY(hipGetLastError());
   return MR_OK;
 }

@@ -12,6 +12,7 @@
 #include "mr_track.h"
 #include "mr_agent.h"
 #include "mr_plant.h"
+#include "mr_tyrefit.h"
 
 using namespace mr;
 
@@ -249,6 +250,102 @@ int mrh_pacejka(const double* a, double Fz, double alpha, int fp32, double* out3
     TyreJet<double> j = pacejka_jet(c, alpha);
     out3[0] = j.v; out3[1] = j.d; out3[2] = j.dd;
   }
+  return 0;
+}
+
+// ---- tyre-model fitting (mr_tyrefit.h): the kernels' wave functions as emulated wavefronts ----
+static thread_local const char* g_tyrefit_err = "";
+static int tyrefit_fail(const char* msg) {
+  g_tyrefit_err = msg;
+  return -1;
+}
+// reason of the last -1 returned by mrh_tyre_loss_grad / mrh_tyre_fit on this thread
+const char* mrh_tyrefit_last_error(void) { return g_tyrefit_err; }
+int mrh_tyrefit_config_default(mr_tyrefit_config* c) {
+  fill_default_tyrefit_config(c);
+  return 0;
+}
+
+struct LossGradJob {
+  const mr_tyrefit_config* cfg;
+  int n, p, chunk, n_chunk;
+  const double *rows, *params, *Fz;
+  double* partials;
+};
+static void lossgrad_body(HostWave* hw, int lane, void* arg) {
+  LossGradJob* j = (LossGradJob*)arg;
+  Wv w{lane, hw};
+  tf_lossgrad_chunk(w, *j->cfg, j->n, j->rows, j->p, j->chunk, j->n_chunk, j->params, j->Fz, j->partials);
+  wsync(w);
+}
+int mrh_tyre_loss_grad(const mr_tyrefit_config* cfg, int n, const double* rows, int P, const double* params,
+                       const double* Fz, double* loss, double* grad) {
+  if (const char* e = tyrefit_check_config(cfg)) return tyrefit_fail(e);
+  if (!rows || !params || !Fz || !loss || !grad) return tyrefit_fail("null argument");
+  if (n < 1) return tyrefit_fail("n < 1");
+  if (P < 1) return tyrefit_fail("P < 1");
+  const int n_chunk = (n + WL - 1) / WL;
+  std::vector<double> partials((size_t)P * n_chunk * TF_NSUM, NAN);
+  for (int p = 0; p < P; ++p)
+    for (int k = 0; k < n_chunk; ++k) {
+      LossGradJob job{cfg, n, p, k, n_chunk, rows, params, Fz, partials.data()};
+      HostWave* hw = new HostWave();
+      host_wave_run(*hw, &lossgrad_body, &job);
+      delete hw;
+    }
+  for (int p = 0; p < P; ++p) tf_lossgrad_finish(*cfg, n, p, n_chunk, partials.data(), params, Fz, loss, grad);
+  return 0;
+}
+
+struct FitJob {
+  const TfFitArgs* A;
+  int run;
+};
+static void fit_body(HostWave* hw, int lane, void* arg) {
+  FitJob* j = (FitJob*)arg;
+  Wv w{lane, hw};
+  if (j->A->cfg.kind == MR_TYRE_PACEJKA) tf_fit_run<MR_TYRE_PACEJKA>(*j->A, j->run, w);
+  else tf_fit_run<MR_TYRE_LINEAR>(*j->A, j->run, w);
+  wsync(w);
+}
+int mrh_tyre_fit(const mr_tyrefit_config* cfg, int n_train, const double* train, int n_val, const double* val, int R,
+                 const double* init, const double* Fz, const double* hyper, const int32_t* perm,
+                 int64_t perm_stride_run, double* p_final, double* p_best, double* train_loss, double* val_loss,
+                 double* lr_hist, int32_t* flag, double* p_steps, int nthreads) {
+  if (const char* e = tyrefit_check_fit(cfg, n_train, n_val, R, perm_stride_run)) return tyrefit_fail(e);
+  if (!train || !val || !init || !Fz || !hyper || !perm || !p_final || !p_best || !train_loss || !val_loss ||
+      !lr_hist || !flag)
+    return tyrefit_fail("null argument");
+  const int64_t per_run = (int64_t)cfg->epochs * n_train;
+  for (int r = 0; r < (perm_stride_run ? R : 1); ++r)
+    for (int64_t k = 0; k < per_run; ++k) {
+      const int32_t v = perm[r * perm_stride_run + k];
+      if (v < 0 || v >= n_train) return tyrefit_fail("perm entry out of range [0, n_train)");
+    }
+  TfFitArgs A;
+  A.cfg = *cfg;
+  A.n_train = n_train; A.n_val = n_val; A.R = R;
+  A.train = train; A.val = val; A.init = init; A.Fz = Fz; A.hyper = hyper;
+  A.perm = perm; A.perm_stride_run = perm_stride_run;
+  A.p_final = p_final; A.p_best = p_best; A.train_loss = train_loss; A.val_loss = val_loss; A.lr_hist = lr_hist;
+  A.flag = flag;
+  A.p_steps = p_steps;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int r = 0; r < R; ++r) {
+    FitJob job{&A, r};
+    HostWave* hw = new HostWave();
+    host_wave_run(*hw, &fit_body, &job);
+    delete hw;
+  }
+  return 0;
+}
+
+// Pacejka force and its parameter gradient dFy/da[0..8] at a slip angle (mr_tyrefit.h), fp64
+int mrh_pacejka_dparams(const double* a, double Fz, double alpha, double* Fy, double* dFy_da) {
+  TfCoef t = tf_coef(a, Fz);
+  double d[4];
+  *Fy = pacejka_partials(t.c, alpha, d);
+  pacejka_chain(t, a, Fz, d, dFy_da);
   return 0;
 }
 

@@ -7,9 +7,11 @@ CSRC = os.path.abspath(os.path.join(HERE, "..", "csrc"))
 PRODUCT_LIB = os.path.join(CSRC, "libmpcracing.so")
 HOST_TWIN_LIB = os.path.join(CSRC, "libmpcracing_host.so")
 
-ABI_VERSION = 102  # MR_ABI_VERSION of include/mpcracing.h
+ABI_VERSION = 103  # MR_ABI_VERSION of include/mpcracing.h
 MR_MODEL = {"kin": 0, "dyn": 1, "blend": 2, "blend_pacejka": 3, "dyn_pacejka": 4}
 MR_PREC = {"fp64": 0, "fp32": 1}
+MR_TYRE = {"linear": 0, "pacejka": 1}
+MR_OPT = {"sgd": 0, "adam": 1, "adamw": 2}
 STATUS = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "failed", 4: "infeasible"}
 
 _I32 = ctypes.c_int32
@@ -42,12 +44,19 @@ class MROutputs(ctypes.Structure):
                                                            ("constr_viol", ctypes.c_void_p)]
 
 
+class MRTyrefitConfig(ctypes.Structure):
+    _fields_ = [(n, _I32) for n in ("kind", "optimizer", "epochs", "patience")] + \
+               [(n, _D) for n in ("factor", "m", "Iz", "lf", "lr", "T_max", "r_wheel", "C_wheel", "R", "rho", "C_d",
+                                  "A_f", "C_roll", "g", "max_steer_deg")]
+
+
 # every symbol declared in include/mpcracing.h (checked by tests/test_abi.py)
 EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_destroy", "mr_set_tyres",
            "mr_solve_batch", "mr_workspace_bytes_per_instance", "mr_eval_dynamics",
            "mr_track_create", "mr_track_destroy", "mr_track_eval", "mr_track_frame", "mr_track_error_sign",
            "mr_track_polyfit", "mr_track_polyfit_deg", "mr_track_lookup_error", "mr_track_projection", "mr_track_prep",
-           "mr_spline_from_waypoints", "mr_track_lane_table", "mr_agent_sense", "mr_plant_step"]
+           "mr_spline_from_waypoints", "mr_track_lane_table", "mr_agent_sense", "mr_plant_step",
+           "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit"]
 
 
 def _bind_product(lib):
@@ -77,6 +86,10 @@ def _bind_product(lib):
     lib.mr_track_lane_table.argtypes = [V, V, _I32, V, V, V, V]
     lib.mr_agent_sense.argtypes = [V, _I32, V, V, V, _D, _D, _D, V, V, V, V, V, V]
     lib.mr_plant_step.argtypes = [_I32, _I32, V, V, _D, V, V]
+    TC = ctypes.POINTER(MRTyrefitConfig)
+    lib.mr_tyrefit_config_default.argtypes = [TC]
+    lib.mr_tyre_loss_grad.argtypes = [TC, _I32, V, _I32, V, V, V, V, V]
+    lib.mr_tyre_fit.argtypes = [TC, _I32, V, _I32, V, _I32, V, V, V, V, ctypes.c_int64, V, V, V, V, V, V, V, V]
     return lib
 
 
@@ -122,4 +135,10 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_lane_table.argtypes = [V, I, _D, I, V, I, _D, I, V, V, V]
     lib.mrh_agent_sense.argtypes = [V, I, _D, I, I, V, V, V, _D, _D, _D, V, V, V, V, V]
     lib.mrh_plant_step.argtypes = [I, I, V, V, _D, V]
+    TC = ctypes.POINTER(MRTyrefitConfig)
+    lib.mrh_tyrefit_config_default.argtypes = [TC]
+    lib.mrh_tyre_loss_grad.argtypes = [TC, I, V, I, V, V, V, V]
+    lib.mrh_tyre_fit.argtypes = [TC, I, V, I, V, I, V, V, V, V, ctypes.c_int64, V, V, V, V, V, V, V, I]
+    lib.mrh_tyrefit_last_error.restype = ctypes.c_char_p
+    lib.mrh_pacejka_dparams.argtypes = [_PD, _D, _D, _PD, _PD]
     return lib

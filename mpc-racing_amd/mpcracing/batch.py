@@ -134,10 +134,13 @@ class BatchSolver:
 
 
 def solver_for_config(name, max_batch, device=0, **kw):
-    """BatchSolver configured as BASELINE config ``name`` (C1..C5)."""
+    """BatchSolver configured as BASELINE config ``name`` (C1..C5); ``tyres=`` replaces the config's
+    learned tyre coefficients (e.g. ``mpcracing.tyrefit.fit_tyres(...).tyres``)."""
     from .workload import CONFIGS, tyre_coeffs
     c = CONFIGS[name]
-    tyres = tyre_coeffs(c["tyres"]) if c["tyres"] else None
+    tyres = kw.pop("tyres", None)
+    if tyres is None:
+        tyres = tyre_coeffs(c["tyres"]) if c["tyres"] else None
     precision = kw.pop("precision", c["precision"])
     return BatchSolver(c["N"], c["model"], precision, c["lane"], c["Ts"], max_batch=max_batch,
                        device=device, tyres=tyres, **kw)
