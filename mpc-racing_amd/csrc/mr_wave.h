@@ -1670,19 +1670,24 @@ struct WaveSolver {
   //   LS_CAP    the first trial's constraint values are also written to the cold fields CTR / CTC, so a
   //             second-order correction of that trial point accumulates them (soc_backward) instead of
   //             evaluating the point again;
+  //   LS_NOSOC  backtracking that never asks for a second-order correction (the resumed backtracking);
   //   otherwise backtracking; a rejected first trial (a0 = the fraction-to-boundary step, theta not
   //   decreased) returns with LS_NEED_SOC so the caller runs the second-order corrections.
+  // MODE is a template argument (every caller passes a literal): an instantiation without LS_CAP -- the
+  // resumed backtracking's, 78 % of a long solve's trials -- has no capture code at all, and the single-trial
+  // modes (LS_WD, LS_FORCE) no backtracking loop.
   // SOCDIR: the trial points lie along the SOC direction (SDZ, SDS) instead of the Newton direction.
   // RESTO: the restoration phase's NLP (mr_solver.h trial() with resto set).
   enum { LS_WD = 1, LS_FORCE = 2, LS_NOSOC = 8, LS_CAP = 16 };
   enum { LSR_ACC = 1, LSR_AUG = 2, LSR_REJF = 4, LSR_NEED_SOC = 8, LSR_FIN = 16 };
-  template <bool RESTO, bool SOCDIR>
-  MR_SWEEP void line_search(T th, T ph, T gphi, T th_pow, T a0, T a_max, T a_min, int nls0, int mode, T a_fix) {
+  template <bool RESTO, bool SOCDIR, int MODE>
+  MR_SWEEP void line_search(T th, T ph, T gphi, T th_pow, T a0, T a_max, T a_min, int nls0, T a_fix) {
     MR_UNIFORM_P();
     MR_ASSUME_LDS_STATE();
 #if MR_PHASE_CYCLES
     const unsigned long long tls0 = trace ? MR_CLOCK() : 0ull;
 #endif
+    constexpr bool CAP = !RESTO && (MODE & LS_CAP) != 0;
     const int nb = 1 - cur;
     const int k = ln;
     const int N = wu(w, this->N);
@@ -1744,13 +1749,50 @@ struct WaveSolver {
     }
     T zt[NZS], st[NI];
     const T kdm = T(IP_KAPPA_D) * mu;
+    // the filter's entries beyond the LDS bank (filter_hit_ov's fields), loaded once per line search: the
+    // filter does not change inside one (filter_add runs after it), and a solve with more than FMAX entries
+    // paid this round trip in every trial's acceptance test
+    const int nf = wu(w, nfilt);
+    T fova[FOVF], fovb[FOVF];
+    if (nf > FMAX) {
+      const int bank = fbank();
+#pragma unroll
+      for (int q = 0; q < FOVF; ++q) {
+        fova[q] = fovb[q] = T(0);
+        if (FMAX + q * WL < nf) {  // (nf wave-uniform)
+          fova[q] = Cf(CSF::FOV + (2 * bank) * FOVF + q);
+          fovb[q] = Cf(CSF::FOV + (2 * bank + 1) * FOVF + q);
+        }
+      }
+    }
+    // filter_ok with the overflow entries in registers: the same comparisons and votes
+    auto filt_ok = [&](T tht, T pht) -> bool {
+      if (filter_hit_lds(tht, pht, nf, &fth(0), &fph(0))) return false;
+      if (nf > FMAX) {
+        int hit = 0;
+#pragma unroll
+        for (int q = 0; q < FOVF; ++q) {
+          const int base = FMAX + q * WL;
+          if (base < nf) hit |= (base + ln < nf && tht >= fova[q] && pht >= fovb[q]) ? 1 : 0;
+        }
+        if (wany(w, hit != 0)) return false;
+      }
+      return true;
+    };
     // one trial point: zt, st (registers), theta, phi; false if a slack is not positive or a value is
-    // not finite.  cap: also write its constraint values to the cold fields CTR / CTC for a second-order
-    // correction (LS_CAP).  One body with a run-time flag: the form with two compile-time instantiations
-    // selected by (capm && n == 0) -- a branch the compiler must treat as divergent, mode being a VGPR
-    // argument -- made the fp64 C5 solves differ from run to run in the second-order-correction steps
-    // (tools/determinism_probe.py; bisected to that change); this form is bit-identical run to run
-    auto eval = [&](T alpha, T& th_t, T& ph_t, bool cap) -> bool {
+    // not finite.  With LS_CAP the point's constraint values (the rows' signed d - s, the dynamics defects;
+    // 0 where nothing is accumulated) are also returned in the registers cr / cc, and one block after the
+    // evaluation stores them to the cold fields CTR / CTC under the wave-uniform test n == 0.  MODE is a
+    // compile-time argument, so there is one evaluation body per instantiation and no branch inside it on
+    // the capture: the round-6 form with two bodies selected inside the loop by (capm && n == 0) -- a
+    // condition the compiler had to treat as divergent, mode being a VGPR argument -- made the fp64 C5
+    // solves differ from run to run (tools/determinism_probe.py).
+    T cr[CAP ? NI : 1], cc[CAP ? NX : 1];
+    if constexpr (CAP) {
+      for (int j = 0; j < NI; ++j) cr[j] = T(0);
+      for (int i = 0; i < NX; ++i) cc[i] = T(0);
+    }
+    auto eval = [&](T alpha, T& th_t, T& ph_t) -> bool {
 #if MR_PHASE_CYCLES
       const unsigned long long te0 = trace ? MR_CLOCK() : 0ull;
 #endif
@@ -1790,9 +1832,9 @@ struct WaveSolver {
             if (yslot(j)) {
               const T r = d[j] - sj;
               th_l += a ? mr_abs(r) : T(0);
-              if (cap) Cf(CSF::CTR + j) = a ? T(slot_sign(j)) * r : T(0);
-            } else if (cap) {
-              Cf(CSF::CTR + j) = T(0);
+              if constexpr (CAP) cr[j] = a ? T(slot_sign(j)) * r : T(0);
+            } else if constexpr (CAP) {
+              cr[j] = T(0);
             }
           }
         }
@@ -1839,11 +1881,11 @@ struct WaveSolver {
           } else {
             for (int i = 0; i < NX; ++i) {
               th_l += mr_abs(xn[i] - ztn[i]);
-              if (cap) Cf(CSF::CTC + i) = xn[i] - ztn[i];
+              if constexpr (CAP) cc[i] = xn[i] - ztn[i];
             }
           }
-        } else if (!RESTO && cap) {
-          for (int i = 0; i < NX; ++i) Cf(CSF::CTC + i) = T(0);
+        } else if constexpr (CAP) {
+          for (int i = 0; i < NX; ++i) cc[i] = T(0);
         }
       }
 #if MR_PHASE_CYCLES
@@ -1883,20 +1925,26 @@ struct WaveSolver {
     int nls = nls0, ntr = 0;
     int flags = 0;
     bool store = false;
-    if (mode & LS_FORCE) {
+    if constexpr ((MODE & LS_FORCE) != 0) {
       alpha = a_fix;
-      const bool fin = eval(alpha, th_t, ph_t, false);
+      const bool fin = eval(alpha, th_t, ph_t);
       ntr++;
       flags |= fin ? LSR_FIN : 0;
       store = true;
       ph_acc = ph_t;  // (the forced trial's own barrier objective: the soft restoration's test)
     } else {
-      const bool capm = !RESTO && (mode & LS_CAP);
-      for (int n = 0; n < IP_LS_MAX; ++n) {
+      constexpr int NTRIAL = (MODE & LS_WD) ? 1 : IP_LS_MAX;  // (LS_WD: its one trial, no loop)
+      for (int n = 0; n < NTRIAL; ++n) {
         if (!(alpha > a_min || n == 0)) break;
-        a_test = (mode & LS_WD) ? a_fix : alpha;
-        const bool fin = eval(alpha, th_t, ph_t, capm && n == 0);
+        a_test = (MODE & LS_WD) ? a_fix : alpha;
+        const bool fin = eval(alpha, th_t, ph_t);
         ntr++;
+        if constexpr (CAP) {
+          if (n == 0 && own()) {  // (n wave-uniform: the loop counter)
+            for (int j = 0; j < NI; ++j) Cf(CSF::CTR + j) = cr[j];
+            for (int i = 0; i < NX; ++i) Cf(CSF::CTC + i) = cc[i];
+          }
+        }
 #if MR_PHASE_CYCLES
         const unsigned long long ta0 = trace ? MR_CLOCK() : 0ull;
 #endif
@@ -1907,7 +1955,7 @@ struct WaveSolver {
             if (a_test > T(0) && ftype(a_test) && th <= theta_min) ok = armijo(ph_t, a_test, ref);
             else ok = acc_it(th_t, ph_t);
           }
-          if (ok && !filter_ok(th_t, ph_t)) { ok = false; flags |= LSR_REJF; }
+          if (ok && !filt_ok(th_t, ph_t)) { ok = false; flags |= LSR_REJF; }
         }
 #if MR_PHASE_CYCLES
         if (trace) tsub[10] += MR_CLOCK() - ta0;
@@ -1919,17 +1967,22 @@ struct WaveSolver {
           store = true;
           break;
         }
-        if (mode & LS_WD) {  // the single trial is stored either way: the watchdog takes it anyway if its
-          store = true;      // trial budget lasts (no re-evaluation); otherwise the point is overwritten
+        if constexpr ((MODE & LS_WD) != 0) {
+          // the watchdog's single trial is stored either way: the watchdog takes it anyway if its trial
+          // budget lasts (no re-evaluation); otherwise the point is overwritten.  A rejected second-order
+          // correction's trial point (SOCDIR) is read by nobody -- the next correction needs only its
+          // captured constraint values -- and is not stored
+          store = !SOCDIR;
           flags |= fin ? LSR_FIN : 0;
           break;
+        } else {
+          if (!RESTO && !(MODE & LS_NOSOC) && fin && n == 0 && alpha == a_max && theta <= th_t) {
+            flags |= LSR_NEED_SOC;  // the caller runs the second-order corrections, then resumes at alpha/2
+            break;
+          }
+          alpha *= T(0.5);
+          nls++;
         }
-        if (!RESTO && !(mode & LS_NOSOC) && fin && n == 0 && alpha == a_max && theta <= th_t) {
-          flags |= LSR_NEED_SOC;  // the caller runs the second-order corrections, then resumes at alpha/2
-          break;
-        }
-        alpha *= T(0.5);
-        nls++;
       }
     }
     if (store && own()) {  // the chosen point
@@ -2794,7 +2847,7 @@ struct WaveSolver {
   // res_alpha = a.
   MR_HD int soft_resto(T th, T ph, T gphi, T th_pow, T ap, T ad) {
     const T a = mr_min(ap, ad);
-    line_search<false, false>(th, ph, gphi, th_pow, a, a, a, 0, LS_FORCE, a);
+    line_search<false, false, LS_FORCE>(th, ph, gphi, th_pow, a, a, a, 0, a);
     if (!(res_flags & LSR_FIN)) return 0;
     const T th_t = res_th, ph_t = res_ph;
     const LSRef<T> ref{th, ph, gphi, th_pow};
@@ -2997,7 +3050,7 @@ struct WaveSolver {
       T a_min = alpha_min_of(th, gphi);
       if (rs) {  // a restoration-phase step: its own filter, no watchdog, no second-order correction
         MR_T0();
-        line_search<true, false>(th, ph, gphi, th_pow, ap, ap, a_min, 0, 0, T(0));
+        line_search<true, false, 0>(th, ph, gphi, th_pow, ap, ap, a_min, 0, T(0));
         MR_T1(3);
         MR_STAT((st_resto++, st_trials += res_ntr));
         if (!(res_flags & LSR_ACC)) { out.status = 3; break; }  // IPOPT: restoration failed
@@ -3066,12 +3119,12 @@ struct WaveSolver {
         }
         if (tiny) {  // IPOPT: a tiny step is taken without a line search (and, with small multiplier steps,
                      // forces a barrier decrease)
-          line_search<false, false>(th, ph, gphi, th_pow, ap, ap, ap, 0, LS_FORCE, ap);
+          line_search<false, false, LS_FORCE>(th, ph, gphi, th_pow, ap, ap, ap, 0, ap);
           accepted = true;
           cw()->tiny = ysmall ? 1 : 0;
         } else if (wuni(w, cw()->in_wd != 0)) {
           auto* C = cw();
-          line_search<false, false>(C->wd_th, C->wd_ph, C->wd_gphi, C->wd_thpow, ap, ap, ap, 0, LS_WD, C->wd_ap);
+          line_search<false, false, LS_WD>(C->wd_th, C->wd_ph, C->wd_gphi, C->wd_thpow, ap, ap, ap, 0, C->wd_ap);
           flags = res_flags;
           rejf |= (flags & LSR_REJF) != 0;
           uth = C->wd_th;
@@ -3092,7 +3145,7 @@ struct WaveSolver {
             th_pow = C->wd_thpow;
             uth = th;
             uph = ph;
-            line_search<false, false>(th, ph, gphi, th_pow, T(0.5) * ap, ap, a_min, 1, LS_NOSOC, T(0));
+            line_search<false, false, LS_NOSOC>(th, ph, gphi, th_pow, T(0.5) * ap, ap, a_min, 1, T(0));
             flags = res_flags;
             rejf |= (flags & LSR_REJF) != 0;
             accepted = (flags & LSR_ACC) != 0;
@@ -3104,7 +3157,7 @@ struct WaveSolver {
 #else
 #define MR_TQ(q) ((void)0)
 #endif
-          line_search<false, false>(th, ph, gphi, th_pow, ap, ap, a_min, 0, LS_CAP, T(0));
+          line_search<false, false, LS_CAP>(th, ph, gphi, th_pow, ap, ap, a_min, 0, T(0));
           MR_TQ(16);
           flags = res_flags;
           rejf |= (flags & LSR_REJF) != 0;
@@ -3140,8 +3193,7 @@ struct WaveSolver {
 #if MR_PHASE_CYCLES
               if (trace) tq = MR_CLOCK();
 #endif
-              line_search<false, true>(th, ph, gphi, th_pow, aps, aps, aps, 0, LS_WD | LS_CAP,
-                                       a_test0);
+              line_search<false, true, LS_WD | LS_CAP>(th, ph, gphi, th_pow, aps, aps, aps, 0, a_test0);
               MR_TQ(18);
               rejf |= (res_flags & LSR_REJF) != 0;
               a_soc = aps;
@@ -3159,7 +3211,7 @@ struct WaveSolver {
 #if MR_PHASE_CYCLES
               if (trace) { tsub[23] += 1; tq = MR_CLOCK(); }
 #endif
-              line_search<false, false>(th, ph, gphi, th_pow, T(0.5) * a_trial, ap, a_min, 1, LS_NOSOC, T(0));
+              line_search<false, false, LS_NOSOC>(th, ph, gphi, th_pow, T(0.5) * a_trial, ap, a_min, 1, T(0));
               MR_TQ(20);
               flags = res_flags;
               rejf |= (flags & LSR_REJF) != 0;

@@ -1,0 +1,62 @@
+"""Generator of tests/golden/tail_parent.npz (tests/test_gpu_tail_golden.py).
+
+Every output array of three small GPU solves, recorded with the product library of the commit *before*
+the line-search restructure (compile-time modes, hoisted filter overflow entries), which changes no
+arithmetic: the outputs must stay bitwise equal.  Run on the GPU from the repository root:
+
+    python tests/golden/make_tail_golden.py [OUT.npz]
+
+Cases (keys "<case>/<array>", plus "<case>/idx" = the instances' indices in rank 0's shard):
+  C4    fp32, 64 instances: the shard's long solves 4341, 2586, 4765, 3049, 312, 395, 844, 2592 (second-order
+        corrections, resumed backtracking to alpha_min, watchdog, overflowing filter) plus instances 0..55
+  C5    fp32, the first 32 instances
+  C3    fp64, the first 32 instances (lane rows, restoration line search)
+"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "..", "..", "mpc-racing_amd"))
+
+C4_LONG = [4341, 2586, 4765, 3049, 312, 395, 844, 2592]
+CASES = {
+    "C4": ("C4", "fp32", C4_LONG + list(range(56))),
+    "C5": ("C5", "fp32", list(range(32))),
+    "C3": ("C3", "fp64", list(range(32))),
+}
+
+
+def case_batch(case):
+    """(config name, precision, index array, the batch of exactly those instances)."""
+    from mpcracing import workload as wl
+    name, precision, idx = CASES[case]
+    idx = np.asarray(idx, dtype=np.int64)
+    b = wl.make_batch(name, limit=int(idx.max()) + 1)
+    sub = {k: (np.ascontiguousarray(v[..., idx]) if v is not None else None) for k, v in b.items()}
+    return name, precision, idx, sub
+
+
+def solve_case(case):
+    from mpcracing.batch import solver_for_config
+    name, precision, idx, sub = case_batch(case)
+    out = solver_for_config(name, len(idx), precision=precision).solve(sub)
+    return idx, {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def main():
+    dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "tail_parent.npz")
+    arrays = {}
+    for case in CASES:
+        idx, out = solve_case(case)
+        arrays[f"{case}/idx"] = idx
+        for k, v in out.items():
+            arrays[f"{case}/{k}"] = v
+        print(case, "iters max", int(out["iters"].max()), "status", np.bincount(out["status"]).tolist(), flush=True)
+    np.savez_compressed(dst, **arrays)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+
+
+if __name__ == "__main__":
+    main()
