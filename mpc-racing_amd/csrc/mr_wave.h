@@ -112,10 +112,12 @@ struct CSF {
   enum {
     WZ = 0, WSL = WZ + NZS, WLAM = WSL + NI, WDZ = WLAM + NI, WDS = WDZ + NZS, WDLAM = WDS + NI,
     WDNU = WDLAM + NI, WY = WDNU + NX, WDY = WY + NI,
-    // second-order corrections: right-hand sides c_soc / r_soc, the direction, the vector pass (g_soc,
-    // costate p, feed-forward k); the restoration entry point; IPOPT's stored acceptable iterate
-    SC = WDY + NI, SR = SC + NX, SG = SR + NI, SPV = SG + NZ, SK0 = SPV + NX, SDZ = SK0 + NU, SDS = SDZ + NZS,
-    SDLAM = SDS + NI, SDY = SDLAM + NI, SDNU = SDY + NI, RS0 = SDNU + NX, RLAM = RS0 + NI, AZ = RLAM + NI,
+    // second-order corrections: right-hand sides c_soc / r_soc, the vector pass (g_soc, costate p; the
+    // recursions' constants and the feed-forward k live in LDS), the direction's primal side (its dual side
+    // is formed by soc_commit, for an accepted correction only); the restoration entry point; IPOPT's stored
+    // acceptable iterate
+    SC = WDY + NI, SR = SC + NX, SG = SR + NI, SPV = SG + NZ, SDZ = SPV + NX, SDS = SDZ + NZS,
+    RS0 = SDS + NI, RLAM = RS0 + NI, AZ = RLAM + NI,
     ASL = AZ + NZS, ALAM = ASL + NI, AY = ALAM + NI,  // the stored acceptable point's slacks and multipliers
     RP = AY + NI, RN = RP + NI, RVP = RN + NI, RVN = RVP + NI, RDP = RVN + NI, RDN = RDP + NI, RDVP = RDN + NI,
     RDVN = RDVP + NI, RY = RDVN + NI, RDY = RY + NI, RZ = RDY + NI,
@@ -1312,8 +1314,9 @@ struct WaveSolver {
 
 
   // The forward recursion of sweep 3 (dz of the lane's stage, from LDS): the Newton direction, or with SOCM
-  // the second-order correction's (feed-forward k_soc, constant c_soc, costate p_soc from the SOC's cold
-  // fields, its costate step to SDNU) -- the same lane-group recursion for both.
+  // the second-order correction's primal side -- the same lane-group recursion without the costate group
+  // (soc_commit forms an accepted correction's costate step), its constants (c_soc, feed-forward k_soc) read
+  // from the LDS slots the step's results go to, where soc_backward's last section put them.
   template <bool SOCM>
   MR_HD void fwd_recursion(T* dz) {
     {
@@ -1333,7 +1336,7 @@ struct WaveSolver {
       // afterwards (a different cache line per lane and load).  Lanes without a row read the
       // record's zero slot; E^'s structural entries come from the record's constant slots.
       const int grp = ln >> 4, r = ln & 15;
-      const bool g0r = (grp == 0) & (r < NX), g1r = (grp == 1) & (r < NX), g2r = (grp == 2) & (r < NU);
+      const bool g0r = (grp == 0) & (r < NX), g1r = !SOCM && (grp == 1) & (r < NX), g2r = (grp == 2) & (r < NU);
       const int r0 = g0r ? r : 0;
       int roff[NX], boff[NU], c0off;
 #pragma unroll
@@ -1343,18 +1346,17 @@ struct WaveSolver {
 #pragma unroll
       for (int a = 0; a < NU; ++a) boff[a] = ehat_slot(r0, NX + a, g0r);
       c0off = g0r ? ehat_slot(r0, 14, true) : (g1r ? RCF::PV0 + r : (g2r ? RCF::K0 + r : RCF::CZERO));
-      // SOCM: the constants come from the SOC's cold fields (c_soc, its costate vector, its feed-forward)
-      // of stage kk, one extra gather per stage; lanes without a row keep the record's zero slot
-      const bool cold_c = SOCM && (g0r | g1r | g2r);
-      const unsigned cold0 = (unsigned)(SSF::NF * WL) + (unsigned)RC_STRIDE * WL;  // cold fields' base word
-      const unsigned ccoff = g0r ? (unsigned)(CSF::SC + r) * WL : (g1r ? (unsigned)(CSF::SPV + r) * WL
-                                                                       : (unsigned)(CSF::SK0 + (g2r ? r : 0)) * WL);
       static_assert(3 * WL <= LP_OFF + 16 * LDS_LD, "du staging");
       // LDS target of each lane's step result (branch-free, one store): group 0 dx_{k+1}[r] at
       // LDX[(k + 1) 12 + r] (row N + 1 <= 64; N = 63: the discard slots), group 2 du_k[r] at
       // [LX_OFF + 3 k + r] (the Riccati tiles are dead here), the others their discard slot
       const int lbase = g0r ? LDX_OFF + 12 + r : (g2r ? LX_OFF + r : LJUNK_OFF + ln);
       const int lstep = g0r ? 12 : (g2r ? 3 : 0);
+      // SOCM: stage kk's constant (group 0: c_soc,kk[r], group 2: the SOC's feed-forward) waits in the slot the
+      // step's result overwrites (soc_backward's last section); read with the row gathers, two stages ahead of
+      // that store.  (Stage N's slots hold no constant: its step's results -- row N + 1, du_N -- are read by
+      // nobody.)
+      MR_LDS T* const LB = lds;
       T dxi = T(0);
       if (ln < NX) LDX[ln] = T(0);
       // Row gathers run two stages ahead in three rotating register sets, the loop unrolled by three
@@ -1370,10 +1372,13 @@ struct WaveSolver {
         for (int j = 0; j < NX; ++j) f.rw[j] = wb.ld(ro, (unsigned)roff[j]);
 #pragma unroll
         for (int a = 0; a < NU; ++a) f.bw[a] = wb.ld(ro, (unsigned)boff[a]);
-        f.c0 = wb.ld(ro, (unsigned)c0off);
         if constexpr (SOCM) {
-          const T cc = wb.ld(cold0 + (unsigned)kk, ccoff);
-          f.c0 = cold_c ? cc : f.c0;
+          // unconditional, every lane (a select between this and the record's constant compiled to a branch
+          // around the LDS read that waited for every gather in flight): a lane without a row reads its
+          // discard slot, and its result goes back there
+          f.c0 = LB[lbase + lstep * kk];
+        } else {
+          f.c0 = wb.ld(ro, (unsigned)c0off);
         }
       };
       auto fstep = [&](int k, const FwdRow& f) {
@@ -1388,8 +1393,8 @@ struct WaveSolver {
         dxi = g0r ? accx : T(0);
         lds[lbase + lstep * k] = g0r ? accx : acc;
         const bool dn = g1r & (k >= 1 || !MR_KKT_RESTATED);  // k = 0: the initial-state rows' multiplier step
-        if constexpr (SOCM) {  // the SOC's costate step to its cold field (branch-free: others the discard slot)
-          wb.st(acc, (unsigned)k, dn ? cold0 + (unsigned)(CSF::SDNU + r) * WL : R(k) + RCF::JUNK - (unsigned)k);
+        if constexpr (SOCM) {  // (no costate group: nothing leaves the step but its LDS result)
+          (void)dn;
         } else if constexpr (SSL) {
           if (dn) ss[(SSF::DNU + r) * WL + k] = acc;
         } else {  // branch-free: other lanes write stage k's record discard slot
@@ -1476,9 +1481,11 @@ struct WaveSolver {
   }
 
   // IPOPT's row steps of this lane's stage (mr_solver.h Solver::forward): the slack step of each row
-  // ds = a.dz + (d - s) (SOC: + the correction's r_soc instead of d - s), the distance steps (a two-sided
-  // row's upper distance: -ds), bound-dual steps dv = mu/t - v - (v/t) dt, the multiplier step
-  // dy = (Sigma_s + delta) ds + grad_s phi - y; into the regular fields or the SOC's (SOC)
+  // ds = a.dz + (d - s), the distance steps (a two-sided row's upper distance: -ds), bound-dual steps
+  // dv = mu/t - v - (v/t) dt, the multiplier step dy = (Sigma_s + delta) ds + grad_s phi - y.
+  // SOC (soc_commit): the dual side of an accepted correction -- its slack steps are forward_soc's (SDS,
+  // row_steps_soc_primal: a.dz + r_soc), from which dv and dy follow by the same expressions; only DLAM, DY
+  // and the dual step limit are produced (d, adz, ap_l, g_l unused)
   template <bool SOC>
   MR_HD void row_steps(const T* d, const int* act, const T* adz, T tau, T& ap_l, T& ad_l, T& g_l) {
     const T mu = this->mu, dl = cw()->delta_it, kd = T(IP_KAPPA_D);
@@ -1492,17 +1499,17 @@ struct WaveSolver {
       const T s0 = l0 / t0, s1 = l1 / t1;
       T dt0, dt1, dy0, dy1;
       if (r < 2) {
-        const T R0 = SOC ? Cf(CSF::SR + j0) : d[j0] - t0;
-        const T R1 = SOC ? Cf(CSF::SR + j1) : -(d[j1] - t1);
-        const T Ds0 = adz[j0] + R0, Ds1 = -adz[j1] + R1;
+        const T R0 = SOC ? T(0) : d[j0] - t0;
+        const T R1 = SOC ? T(0) : -(d[j1] - t1);
+        const T Ds0 = SOC ? Cf(CSF::SDS + j0) : adz[j0] + R0, Ds1 = SOC ? -Cf(CSF::SDS + j1) : -adz[j1] + R1;
         dt0 = Ds0;
         dt1 = -Ds1;
         dy0 = (s0 + dl) * Ds0 - mu / t0 + kd * mu - S(SSF::Y + j0);
         dy1 = (s1 + dl) * Ds1 + mu / t1 - kd * mu - S(SSF::Y + j1);
         if (!SOC) g_l += a ? kd * mu * (dt0 + dt1) : T(0);
       } else {
-        const T R0 = SOC ? Cf(CSF::SR + j0) : d[j0] - t0;
-        const T Ds = adz[j0] + R0;
+        const T R0 = SOC ? T(0) : d[j0] - t0;
+        const T Ds = SOC ? Cf(CSF::SDS + j0) : adz[j0] + R0;
         dt0 = Ds;
         dt1 = -Ds;
         dy0 = (s0 + s1 + dl) * Ds - mu / t0 + mu / t1 - S(SSF::Y + j0);
@@ -1510,20 +1517,45 @@ struct WaveSolver {
       }
       T dv0 = mu / t0 - l0 - s0 * dt0, dv1 = mu / t1 - l1 - s1 * dt1;
       if (!a) { dt0 = dt1 = dv0 = dv1 = dy0 = dy1 = T(0); }
-      if constexpr (SOC) {
-        Cf(CSF::SDS + j0) = dt0; Cf(CSF::SDS + j1) = dt1;
-        Cf(CSF::SDLAM + j0) = dv0; Cf(CSF::SDLAM + j1) = dv1;
-        Cf(CSF::SDY + j0) = dy0; Cf(CSF::SDY + j1) = dy1;
+      if constexpr (SOC) {  // soc_commit: the primal side (SDS) is forward_soc's; here its dual side
+        S(SSF::DLAM + j0) = dv0; S(SSF::DLAM + j1) = dv1;
+        S(SSF::DY + j0) = dy0; S(SSF::DY + j1) = dy1;
       } else {
         S(SSF::DS + j0) = dt0; S(SSF::DS + j1) = dt1;
         S(SSF::DLAM + j0) = dv0; S(SSF::DLAM + j1) = dv1;
         S(SSF::DY + j0) = dy0; S(SSF::DY + j1) = dy1;
         g_l -= mu * dt0 / t0 + mu * dt1 / t1;
       }
-      ap_l = dt0 < T(0) ? mr_min(ap_l, -tau * t0 / dt0) : ap_l;
-      ap_l = dt1 < T(0) ? mr_min(ap_l, -tau * t1 / dt1) : ap_l;
+      if (!SOC) ap_l = dt0 < T(0) ? mr_min(ap_l, -tau * t0 / dt0) : ap_l;
+      if (!SOC) ap_l = dt1 < T(0) ? mr_min(ap_l, -tau * t1 / dt1) : ap_l;
       ad_l = dv0 < T(0) ? mr_min(ad_l, -tau * l0 / dv0) : ad_l;
       ad_l = dv1 < T(0) ? mr_min(ad_l, -tau * l1 / dv1) : ad_l;
+    }
+  }
+  // The primal side of a correction's row steps (row_steps<true>'s ds, the same expressions): the slack steps
+  // to SDS and the fraction-to-boundary primal step size -- all that the correction's trial needs
+  MR_HD void row_steps_soc_primal(const int* act, const T* adz, T tau, T& ap_l) {
+#pragma unroll
+    for (int r = 0; r <= NROW; ++r) {
+      const int j0 = r < NROW ? 2 * r : JL, j1 = j0 + 1;
+      if (!act[j0]) continue;
+      const T t0 = S(sf(cur) + j0), t1 = S(sf(cur) + j1);
+      T dt0, dt1;
+      if (r < 2) {
+        const T R0 = Cf(CSF::SR + j0);
+        const T R1 = Cf(CSF::SR + j1);
+        const T Ds0 = adz[j0] + R0, Ds1 = -adz[j1] + R1;
+        dt0 = Ds0;
+        dt1 = -Ds1;
+      } else {
+        const T R0 = Cf(CSF::SR + j0);
+        const T Ds = adz[j0] + R0;
+        dt0 = Ds;
+        dt1 = -Ds;
+      }
+      Cf(CSF::SDS + j0) = dt0; Cf(CSF::SDS + j1) = dt1;
+      ap_l = dt0 < T(0) ? mr_min(ap_l, -tau * t0 / dt0) : ap_l;
+      ap_l = dt1 < T(0) ? mr_min(ap_l, -tau * t1 / dt1) : ap_l;
     }
   }
 
@@ -2036,16 +2068,17 @@ struct WaveSolver {
   // CSF::SR), c_soc = alpha c_soc + c(trial) per correction (accumulated in soc_backward's stage-parallel pass).
   // Up to max_soc = 4 per iteration; the batch's long solves run 2-3 per iteration, so the two recursions
   // (socb_chain backward, fwd_recursion<true> forward) are lane recursions on the stage records.
-  // The SOC costate recursion given v_k, u_k (cold fields SPV, SK0: everything that does not depend on
-  // pv_{k+1}): pv_k = v_k + A_k^T pv_{k+1} + K_k^T b_k with b_k = B_k^T pv_{k+1}, and r_k = b_k + u_k (the
-  // feed-forward's right-hand side).  Two lane groups share one 11-term dot product with pv_{k+1} (broadcast
+  // The SOC costate recursion given v_k, u_k (everything that does not depend on pv_{k+1}; in the LDS slots
+  // of the recursion's results: LDX row k, [LX_OFF + 3 k]): pv_k = v_k + A_k^T pv_{k+1} + K_k^T b_k with
+  // b_k = B_k^T pv_{k+1}, and r_k = b_k + u_k (the feed-forward's right-hand side).  Two lane groups share one 11-term dot product with pv_{k+1} (broadcast
   // from lanes 0..10 by v_readlane), each lane gathering its coefficient column of the stage map E^ from the
   // record (ehat_slot: its data word or the record's constant slots): group 0 (lanes 0..10) column i of A_k
   // -> (A_k^T pv)[i], group 1 (lanes 16..18) column a of B_k -> b_k[a]; then group 0 adds K_k^T b_k with b_k
   // read from group 1 (the forward recursion's structure, transposed).  B_k^T pv is thus three lanes' dot
-  // products instead of twelve FMAs in every lane.  Per stage: 14 v_readlane, ~16 FMAs, 15 single-line
-  // gathers issued two stages ahead; results to LDS only (pv_k to LDX row k, r_k to [LX_OFF + 3 k]), so the
-  // in-order vmcnt waits for the prefetched operands stay exact.
+  // products instead of twelve FMAs in every lane.  Per stage: 14 v_readlane, ~16 FMAs, 14 single-line
+  // gathers and the constant's LDS read issued two stages ahead; results to LDS only (pv_k to LDX row k, r_k
+  // to [LX_OFF + 3 k], each over the lane's constant of that stage), so the in-order vmcnt waits for the
+  // prefetched operands stay exact.
   MR_HD void socb_chain() {
     const int N = wu(this->w, this->N), ln = this->ln;
     const Wv w = this->w;
@@ -2056,31 +2089,30 @@ struct WaveSolver {
     const bool g0r = (grp == 0) & (r < NX), g1r = (grp == 1) & (r < NU);
     const int li = g0r ? r : 0;
     // per-lane gather plan: the coefficient column (E^ column r of A, or column 11 + r of B), K_k[0..2][r]
-    // (group 0), and the constant v_k[r] (group 0) / u_k[r] (group 1) from the cold fields
+    // (group 0); the constant v_k[r] (group 0) / u_k[r] (group 1) from the lane's LDS slot of stage k
     int coff[NX], koff[NU];
 #pragma unroll
     for (int j = 0; j < NX; ++j) coff[j] = g0r ? ehat_slot(j, r, true) : (g1r ? ehat_slot(j, NX + r, true) : RCF::CZERO);
 #pragma unroll
     for (int a = 0; a < NU; ++a) koff[a] = g0r ? RCF::K + a * NX + r : RCF::CZERO;
-    const unsigned voff = g0r ? (unsigned)(CSF::SPV + r) * WL : (g1r ? (unsigned)(CSF::SK0 + r) * WL : (unsigned)CSF::SJUNK * WL);
-    struct Ops {
-      T c[NX], kc[NU], v;
-    };
-    auto ld = [&](int k, Ops& o) {
-      const unsigned rk = (unsigned)wu(w, (int)R(k)), ck = (unsigned)wu(w, (int)(cold0 + (unsigned)k));
-#pragma unroll
-      for (int j = 0; j < NX; ++j) o.c[j] = wb.ld(rk, (unsigned)coff[j]);
-#pragma unroll
-      for (int a = 0; a < NU; ++a) o.kc[a] = wb.ld(rk, (unsigned)koff[a]);
-      o.v = wb.ld(ck, voff);
-    };
-    T pv = wb.ld((unsigned)wu(w, (int)(cold0 + (unsigned)N)), (unsigned)(CSF::SG + li) * WL);  // pv_N = g_x,N
     // the LDS base in a register (a member read after an LDS store is reloaded from the solver object,
     // itself in LDS: one LDS round trip per step); group 0: LDX row k, group 1: r_k's slot, others: the
     // lane's discard slot
     MR_LDS T* const LB = lds;
     const int pbase = g0r ? LDX_OFF + r : (g1r ? LX_OFF + r : LJUNK_OFF + ln), pstride = g0r ? 12 : (g1r ? 3 : 0);
-    if (g0r) lds[LDX_OFF + N * 12 + r] = pv;
+    struct Ops {
+      T c[NX], kc[NU], v;
+    };
+    auto ld = [&](int k, Ops& o) {
+      const unsigned rk = (unsigned)wu(w, (int)R(k));
+#pragma unroll
+      for (int j = 0; j < NX; ++j) o.c[j] = wb.ld(rk, (unsigned)coff[j]);
+#pragma unroll
+      for (int a = 0; a < NU; ++a) o.kc[a] = wb.ld(rk, (unsigned)koff[a]);
+      o.v = LB[pbase + pstride * k];  // (stage k's step overwrites it: every load of it is issued before)
+    };
+    T pv = wb.ld((unsigned)wu(w, (int)(cold0 + (unsigned)N)), (unsigned)(CSF::SG + li) * WL);  // pv_N = g_x,N
+    if (g0r) LB[LDX_OFF + N * 12 + r] = pv;
     auto step = [&](int k, const Ops& o) {
       T p[NX];
       wgather<T, NX>(w, pv, p);
@@ -2205,7 +2237,7 @@ struct WaveSolver {
     wsync(w);
     MR_TSUB(12);
     // pv_k = Acl_k^T pv_{k+1} + v_k with v_k = A_k^T q + K_k^T u_k + g_x, q = P_{k+1} c_k, u_k = B_k^T q + g_u
-    // (then r_k = B_k^T pv_{k+1} + u_k): v_k, u_k stage-parallel into the cold fields SPV / SK0 (everything
+    // (then r_k = B_k^T pv_{k+1} + u_k): v_k, u_k stage-parallel into the chain's LDS slots (everything
     // that does not depend on pv_{k+1}), then the lean lane recursion (socb_chain: pv_{k+1} broadcast,
     // A_k^T pv + K_k^T (B_k^T pv) + v_k, r_k on the way), then the feed-forward stage-parallel
     if (own() && ln < N) {
@@ -2226,18 +2258,29 @@ struct WaveSolver {
       apply_Bt(J, k, q, u);
       for (int a = 0; a < NU; ++a) u[a] += Cf(CSF::SG + NX + a);
       apply_At(J, k, q, at);
+      // v_k, u_k into the LDS slots the chain's results of stage k go to (lane k writes its own row): the
+      // chain lane reads its constant from the slot it overwrites at the end of the step
       for (int r = 0; r < NX; ++r) {
         T v = at[r] + Cf(CSF::SG + r);
         for (int a = 0; a < NU; ++a) v += Kr[a][r] * u[a];
-        Cf(CSF::SPV + r) = v;
+        lds[LDX_OFF + k * 12 + r] = v;
       }
-      for (int a = 0; a < NU; ++a) Cf(CSF::SK0 + a) = u[a];
+      for (int a = 0; a < NU; ++a) lds[LX_OFF + 3 * k + a] = u[a];
     }
     MR_LDS T* const LDX = lds + LDX_OFF;
-    wsync(w);  // v_k, u_k (cold fields) visible
+    // v_k, u_k visible: LDS only (the section above wrote no global memory; what the chain gathers -- the
+    // records, SG of stage N -- was complete before the sync that ended the first section)
+    wsync_lds(w);
     MR_TSUB(13);
     socb_chain();
     MR_TSUB(14);
+    // The feed-forward stage-parallel, then the forward recursion's constants into the LDS slots its results
+    // of stage k go to (fwd_recursion<true>): the feed-forward k_k to [LX_OFF + 3 k], c_soc,k to LDX row k + 1;
+    // row 0 (dx_0 = 0) is the recursion's.  Every lane reads its pv row and r_k first -- row k + 1 is lane
+    // k + 1's pv row --, an LDS sync, then the writes.  pv_k to the cold field SPV (coalesced) for soc_commit.
+    T kf[NU], cs[NX];
+    for (int a = 0; a < NU; ++a) kf[a] = T(0);
+    for (int r = 0; r < NX; ++r) cs[r] = T(0);
     if (own()) {
       const int k = ln;
       T pv[NX];
@@ -2246,22 +2289,29 @@ struct WaveSolver {
         const MR_GLOBAL T* Rk = R(k);
         const T Lf[6] = {T(0), Rk[RCF::LQ + 0], T(0), Rk[RCF::LQ + 1], Rk[RCF::LQ + 2], T(0)};
         const T iv[3] = {Rk[RCF::LQ + 3], Rk[RCF::LQ + 4], Rk[RCF::LQ + 5]};
-        T kf[NU];
+        for (int r = 0; r < NX; ++r) cs[r] = Cf(CSF::SC + r);
         for (int a = 0; a < NU; ++a) kf[a] = -lds[LX_OFF + 3 * k + a];  // r_k from the chain
         lsolve3r(Lf, iv, kf);
         ltsolve3r(Lf, iv, kf);
-        for (int a = 0; a < NU; ++a) Cf(CSF::SK0 + a) = kf[a];
       }
       for (int r = 0; r < NX; ++r) Cf(CSF::SPV + r) = pv[r];
     }
-    wsync(w);
+    wsync_lds(w);
+    if (own() && ln < N) {
+      const int k = ln;
+      for (int r = 0; r < NX; ++r) LDX[(k + 1) * 12 + r] = cs[r];
+      for (int a = 0; a < NU; ++a) lds[LX_OFF + 3 * k + a] = kf[a];
+    }
+    // LDS only: SPV is read back by the lane that wrote it (soc_commit), nothing here by another lane
+    wsync_lds(w);
     MR_TSUB(15);
 #undef MR_TSUB
   }
-  // the SOC direction (mr_solver.h Solver::forward with soc set): SDZ, SDS, SDLAM, SDY, SDNU.  The recursion
-  // is the Newton direction's (fwd_recursion, its lane groups and prefetch) with the SOC's feed-forward,
-  // constant and costate vector; then stage-parallel the rows' steps and the step limits.
-  MR_SWEEP void forward_soc(T& ap, T& ad) {
+  // the SOC direction's primal side (mr_solver.h Solver::forward with soc set): SDZ, SDS and the primal step
+  // limit -- what the correction's trial needs.  The recursion is the Newton direction's (fwd_recursion, its
+  // lane groups and prefetch) with the SOC's feed-forward and constant; then stage-parallel the rows' slack
+  // steps.  The dual side (DLAM, DY, DNU, the dual step limit) is soc_commit's, for an accepted correction.
+  MR_SWEEP void forward_soc(T& ap) {
     MR_UNIFORM_P();
     MR_ASSUME_LDS_STATE();
     const T tau = mr_max(T(0.99), T(1) - mu);
@@ -2272,18 +2322,15 @@ struct WaveSolver {
     const unsigned long long tc0 = trace ? MR_CLOCK() : 0ull;
 #endif
     fwd_recursion<true>(dzr);
-    wsync(w);  // SDNU (the recursion's costate steps) visible
 #if MR_PHASE_CYCLES
     if (trace) tsub[2] += MR_CLOCK() - tc0;
     const unsigned long long tp0 = trace ? MR_CLOCK() : 0ull;
 #endif
-    T ap_l = T(1), ad_l = T(1), g_l = T(0);
+    T ap_l = T(1);
     if (own()) {
       const int k = ln;
-      const MR_GLOBAL T* Rk = R(k);
       T dz[NZS];
       for (int i = 0; i < NZS; ++i) dz[i] = dzr[i];
-      (void)Rk;
       T z[NZS];
       load_z(cur, z);
       Err<T> e;
@@ -2306,30 +2353,57 @@ struct WaveSolver {
         adz[JL + 1] = -gdz;
       }
       for (int i = 0; i < NZS; ++i) Cf(CSF::SDZ + i) = dz[i];
-      row_steps<true>(d, act, adz, tau, ap_l, ad_l, g_l);
+      row_steps_soc_primal(act, adz, tau, ap_l);
     }
     ap = wmin(w, ap_l);
-    ad = wmin(w, ad_l);
     wsync(w);
 #if MR_PHASE_CYCLES
     if (trace) tsub[3] += MR_CLOCK() - tp0;
 #endif
   }
-  // the accepted correction becomes the iteration's direction; returns its dual step size
+  // the accepted correction becomes the iteration's direction; returns its dual step size.  The direction's
+  // dual side is formed here, once per accepted correction instead of once per try: the rows' bound-dual and
+  // multiplier steps from the slack steps (row_steps<true>), and the costate step of the lane's stage
+  // dnu_k = pv_k + P_k dx_k (the Newton recursion's costate lane group: the constant first, then the terms
+  // in the order j = 0..10), with pv_k from SPV and dx_k from SDZ (the LDS tiles are not the correction's any
+  // more: a line search ran in between)
   MR_SWEEP T soc_commit() {
+    MR_UNIFORM_P();
     MR_ASSUME_LDS_STATE();
     const T tau = mr_max(T(0.99), T(1) - mu);
     T ad_l = T(1);
     if (own()) {
-      for (int i = 0; i < NZS; ++i) S(SSF::DZ + i) = Cf(CSF::SDZ + i);
-      for (int j = 0; j < NI; ++j) {
-        const T dl = Cf(CSF::SDLAM + j), lam = S(SSF::LAM + j);
-        S(SSF::DS + j) = Cf(CSF::SDS + j);
-        S(SSF::DLAM + j) = dl;
-        S(SSF::DY + j) = Cf(CSF::SDY + j);
-        if (lam != T(0) && dl < T(0)) ad_l = mr_min(ad_l, -tau * lam / dl);
+      const int k = ln;
+      const MR_GLOBAL T* Rk = R(k);
+      T dx[NX], pvk[NX], Pk[NP];
+      for (int i = 0; i < NX; ++i) pvk[i] = Cf(CSF::SPV + i);
+      for (int i = 0; i < NP; ++i) Pk[i] = Rk[RCF::P + i];
+      for (int i = 0; i < NZS; ++i) {
+        const T v = Cf(CSF::SDZ + i);
+        if (i < NX) dx[i] = v;
+        S(SSF::DZ + i) = v;
       }
-      for (int i = 0; i < NX; ++i) S(SSF::DNU + i) = Cf(CSF::SDNU + i);
+      for (int j = 0; j < NI; ++j) S(SSF::DS + j) = Cf(CSF::SDS + j);
+      int act[NI];
+#pragma unroll
+      for (int r = 0; r < NROW; ++r) {
+        int a;
+        T lo, hi;
+        row_bounds(P, I, k, r, a, lo, hi);
+        act[2 * r] = act[2 * r + 1] = a;
+      }
+      act[JL] = act[JL + 1] = lane_active(P, k) ? 1 : 0;
+      act[JL + 2] = 0;
+      T ap_l = T(1), g_l = T(0);
+      row_steps<true>((const T*)nullptr, act, (const T*)nullptr, tau, ap_l, ad_l, g_l);
+      if (k >= 1 || !MR_KKT_RESTATED) {  // k = 0: the initial-state rows' multiplier step
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+          T acc = pvk[r];
+          for (int j = 0; j < NX; ++j) acc += Pk[pidx(r, j)] * dx[j];
+          S(SSF::DNU + r) = acc;
+        }
+      }
     }
     const T ad = wmin(w, ad_l);
     wsync(w);
@@ -3185,8 +3259,8 @@ struct WaveSolver {
 #if MR_PHASE_CYCLES
               const unsigned long long ts1 = trace ? MR_CLOCK() : 0ull;
 #endif
-              T aps, ads;
-              forward_soc(aps, ads);
+              T aps;
+              forward_soc(aps);
 #if MR_PHASE_CYCLES
               if (trace) { tsub[6] += ts1 - ts0; tsub[7] += MR_CLOCK() - ts1; }
 #endif
