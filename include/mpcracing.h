@@ -35,7 +35,8 @@ extern "C" {
 /* ABI version (mr_version()): bumped whenever a struct layout or an entry point's meaning changes, so
    a caller built against another header can refuse to run (101: mr_config.dispatch_order,
    mr_outputs.lam_g / timeline, mr_config without lane_penalty (hard lane rows), status 4 = infeasible;
-   102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit) */
+   102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
+   mr_vehicle_step, mr_tyre_rollout) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -302,6 +303,33 @@ int mr_tyre_fit(const mr_tyrefit_config* cfg, int32_t n_train, const double* tra
                 int32_t R, const double* init, const double* Fz, const double* hyper, const int32_t* perm,
                 int64_t perm_stride_run, double* p_final, double* p_best, double* train_loss, double* val_loss,
                 double* lr_hist, int32_t* flag, double* p_steps, void* hip_stream);
+
+/* ---- open-loop rollouts and the fitted model as a plant (csrc/mr_rollout.h) ----------------------------
+ * Which fit is good: the reference rolls a model forward along a logged drive and compares it with what
+ * the car did (learning/compare.py:60, script/verify_dynamic.py, script/test_model_error.py).  The model is
+ * the one-step model of the fit (learning/vehicle.py:136-205) with the tyres of mr_tyrefit_config.kind; the
+ * config's optimiser fields are not read.  All arrays are caller-owned DEVICE pointers. */
+
+/* One model step per vehicle: state [6][n], cmd [2][n] = (throttle - brake, steer) -> out [6][n] (may alias
+   state).  Tyres params [P][n_par], Fz [P][2]: shared (P == 1) or one set per vehicle (P == n).  The
+   model-matched plant of an MPC that carries the same tyres (control/MPC.py:186-229 with the tyre law
+   swapped).  Runs on the device that owns `state`. */
+int mr_vehicle_step(const mr_tyrefit_config* cfg, int32_t n, const double* state, const double* cmd, double dt,
+                    int32_t P, const double* params, const double* Fz, double* out, void* hip_stream);
+/* Rollouts of P parameter sets from n_start start rows over H steps along log [9][T] = X, Y, yaw, vx, vy,
+   yawdot, throttle (cmd_throttle - cmd_brake), steer, ts; ts[i] is last_ts of row i, and the step from row i
+   to row i + 1 uses ts[i + 1] (learning/generate_train_val_datasets.py:41-59).  Start s: x_0 = log[0..5][s],
+   x_k = f(x_{k-1}, throttle[s+k-1], steer[s+k-1], ts[s+k]), error e = log[0..5][s+k] - x_k (truth minus
+   prediction; yaw: the raw difference), k = 1..H.  A rollout whose x_0 or x_k is not finite stops: that step
+   and its later ones contribute nothing.  stats [P][H][6][4] = sum e, sum e^2, min e, max e over the
+   contributing rollouts, count [P][H] their number (count 0: sums 0, min and max NaN); pred: optional
+   [P][H][6][n_start], the predictions (NaN for steps not taken), NULL to skip.  One wavefront per (set, chunk
+   of 64 starts), partial sums added in chunk order: bitwise repeatable, independent of P.  start entries are
+   checked on the device first (MR_ERR_ARG if any is outside [0, T - 1 - H]); the call synchronises the
+   stream before it returns. */
+int mr_tyre_rollout(const mr_tyrefit_config* cfg, int32_t T, const double* log, int32_t n_start, const int32_t* start,
+                    int32_t H, int32_t P, const double* params, const double* Fz, double* stats, int32_t* count,
+                    double* pred, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 #include "mr_agent.h"
 #include "mr_plant.h"
 #include "mr_tyrefit.h"
+#include "mr_rollout.h"
 
 using namespace mr;
 
@@ -337,6 +338,57 @@ int mrh_tyre_fit(const mr_tyrefit_config* cfg, int n_train, const double* train,
     host_wave_run(*hw, &fit_body, &job);
     delete hw;
   }
+  return 0;
+}
+
+// ---- open-loop rollouts and the model as a plant (mr_rollout.h) ----
+int mrh_vehicle_step(const mr_tyrefit_config* cfg, int n, const double* state, const double* cmd, double dt, int P,
+                     const double* params, const double* Fz, double* out) {
+  if (const char* e = vehicle_step_check(cfg, n, P)) return tyrefit_fail(e);
+  if (!state || !cmd || !params || !Fz || !out) return tyrefit_fail("null argument");
+  for (int i = 0; i < n; ++i) {
+    if (cfg->kind == MR_TYRE_PACEJKA) ro_vehicle_step<MR_TYRE_PACEJKA>(*cfg, n, i, state, cmd, dt, P, params, Fz, out);
+    else ro_vehicle_step<MR_TYRE_LINEAR>(*cfg, n, i, state, cmd, dt, P, params, Fz, out);
+  }
+  return 0;
+}
+
+struct RolloutJob {
+  const RoArgs* A;
+  int p, chunk;
+  double* lds;
+};
+static void rollout_body(HostWave* hw, int lane, void* arg) {
+  RolloutJob* j = (RolloutJob*)arg;
+  Wv w{lane, hw};
+  ro_chunk_kind(*j->A, j->p, j->p, j->chunk, j->lds, w);
+  wsync(w);
+}
+int mrh_tyre_rollout(const mr_tyrefit_config* cfg, int T, const double* log, int n_start, const int32_t* start, int H,
+                     int P, const double* params, const double* Fz, double* stats, int32_t* count, double* pred,
+                     int nthreads) {
+  if (const char* e = rollout_check(cfg, T, n_start, H, P)) return tyrefit_fail(e);
+  if (!log || !start || !params || !Fz || !stats || !count) return tyrefit_fail("null argument");
+  for (int k = 0; k < n_start; ++k)
+    if (start[k] < 0 || start[k] > T - 1 - H) return tyrefit_fail("start entry out of range [0, T - 1 - H]");
+  RoArgs A;
+  A.cfg = *cfg;
+  A.T = T; A.n_start = n_start; A.H = H;
+  A.n_chunk = (n_start + WL - 1) / WL;
+  A.log = log; A.start = start; A.params = params; A.Fz = Fz; A.pred = pred;
+  std::vector<double> partials((size_t)P * A.n_chunk * H * RO_NPART, NAN);
+  A.partials = partials.data();
+  const int64_t jobs = (int64_t)P * A.n_chunk;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int64_t b = 0; b < jobs; ++b) {
+    std::vector<double> lds((size_t)RO_LDS_WORDS, NAN);
+    RolloutJob job{&A, (int)(b / A.n_chunk), (int)(b % A.n_chunk), lds.data()};
+    HostWave* hw = new HostWave();
+    host_wave_run(*hw, &rollout_body, &job);
+    delete hw;
+  }
+  for (int p = 0; p < P; ++p)
+    for (int k = 0; k < H; ++k) ro_finish(H, A.n_chunk, partials.data(), p, p, k, stats, count);
   return 0;
 }
 

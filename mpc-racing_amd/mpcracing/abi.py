@@ -56,7 +56,7 @@ EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_
            "mr_track_create", "mr_track_destroy", "mr_track_eval", "mr_track_frame", "mr_track_error_sign",
            "mr_track_polyfit", "mr_track_polyfit_deg", "mr_track_lookup_error", "mr_track_projection", "mr_track_prep",
            "mr_spline_from_waypoints", "mr_track_lane_table", "mr_agent_sense", "mr_plant_step",
-           "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit"]
+           "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout"]
 
 
 def _bind_product(lib):
@@ -90,6 +90,8 @@ def _bind_product(lib):
     lib.mr_tyrefit_config_default.argtypes = [TC]
     lib.mr_tyre_loss_grad.argtypes = [TC, _I32, V, _I32, V, V, V, V, V]
     lib.mr_tyre_fit.argtypes = [TC, _I32, V, _I32, V, _I32, V, V, V, V, ctypes.c_int64, V, V, V, V, V, V, V, V]
+    lib.mr_vehicle_step.argtypes = [TC, _I32, V, V, _D, _I32, V, V, V, V]
+    lib.mr_tyre_rollout.argtypes = [TC, _I32, V, _I32, V, _I32, _I32, V, V, V, V, V, V]
     return lib
 
 
@@ -140,5 +142,7 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_tyre_loss_grad.argtypes = [TC, I, V, I, V, V, V, V]
     lib.mrh_tyre_fit.argtypes = [TC, I, V, I, V, I, V, V, V, V, ctypes.c_int64, V, V, V, V, V, V, V, I]
     lib.mrh_tyrefit_last_error.restype = ctypes.c_char_p
+    lib.mrh_vehicle_step.argtypes = [TC, I, V, V, _D, I, V, V, V]
+    lib.mrh_tyre_rollout.argtypes = [TC, I, V, I, V, I, I, V, V, V, V, V, I]
     lib.mrh_pacejka_dparams.argtypes = [_PD, _D, _D, _PD, _PD]
     return lib

@@ -13,7 +13,10 @@ Here every tick is four device steps on one stream, with no host synchronisation
 1. ``mr_agent_sense``  (csrc/mr_agent.h)  progress, error, cx, cy, max_error for all vehicles;
 2. input glue (torch ops on the device): state0 rows, shifted warm start (MPC.py:120-121);
 3. ``mr_solve_batch``  (csrc/mr_wave.h)   the B MPC solves, one wavefront each;
-4. ``mr_plant_step``   (csrc/mr_plant.h)  one plant step per vehicle with the applied command.
+4. ``mr_plant_step``   (csrc/mr_plant.h)  one plant step per vehicle with the applied command
+   (``plant="learned"``: ``mr_vehicle_step``, csrc/mr_rollout.h -- the one-step model of the tyre fit,
+   learning/vehicle.py:136-205, with ``plant_tyres``: the model-matched plant of an MPC that carries the
+   same learned tyres).
 
 Measurement model: the plant state is the simulator truth; the agent's own derivations are kept
 -- yaw rate by finite differences of the (wrapped) yaw over the tick (agent.py:240-249), the
@@ -21,6 +24,7 @@ commanded throttle fed back as ``cmd_throttle`` / ``cmd_brake`` (agent.py:289-30
 body-frame velocities stand for the agent's rotation of the simulator's world velocity
 (agent.py:252-253).  No CPU fallback: the constructor raises without a GPU.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -38,14 +42,34 @@ LOG_KEYS = ("X", "Y", "yaw", "vx", "vy", "yawdot", "progress", "error", "cmd_thr
 class ClosedLoop:
     def __init__(self, track="shanghai_intl_circuit", B=1, N=15, plant="blend", mpc_model="dyn",
                  precision="fp64", Ts=0.05, dt=0.05, start_control_at=50, lookback=5.0, lookahead=45.0,
-                 runtime=(1000.0, 0.85, 50.0, 2.0, 5000.0), device=0, **solver_kw):
+                 runtime=(1000.0, 0.85, 50.0, 2.0, 5000.0), device=0, plant_tyres=None, plant_kind=None,
+                 **solver_kw):
         if start_control_at < 1:
             raise ValueError("start_control_at >= 1: the MPC's yaw rate is a finite difference over one tick")
         self.track = track if isinstance(track, DeviceTrack) else DeviceTrack(track, device=device)
         self.lib = self.track.lib
         self.dev = self.track.device
         self.B, self.N = int(B), int(N)
-        self.plant = PLANT[plant]
+        self.learned = None
+        if plant == "learned":
+            # plant_tyres: a FitResult (its best run) or (params [n_par] or [B][n_par], Fz or None) with plant_kind
+            from . import rollout, tyrefit
+            if plant_tyres is None:
+                raise ValueError('plant="learned" needs plant_tyres (a FitResult or (params, Fz))')
+            if isinstance(plant_tyres, tyrefit.FitResult):
+                plant_kind = plant_tyres.kind
+                plant_tyres = (plant_tyres.params, plant_tyres.Fz[plant_tyres.best_run])
+            kind, params, Fz = rollout._tyres(plant_tyres, plant_kind or "pacejka")
+            if params.shape[0] not in (1, self.B):
+                raise ValueError(f"plant_tyres: one set or one per vehicle ({self.B}), got {params.shape[0]}")
+            self.learned = dict(cfg=tyrefit.make_config(kind), P=params.shape[0],
+                                params=torch.as_tensor(params, dtype=torch.float64, device=self.dev).contiguous(),
+                                Fz=torch.as_tensor(Fz, dtype=torch.float64, device=self.dev).contiguous())
+            self.plant = None
+        else:
+            if plant_tyres is not None:
+                raise ValueError('plant_tyres goes with plant="learned"')
+            self.plant = PLANT[plant]
         self.dt, self.start_control_at = float(dt), int(start_control_at)
         self.lookback, self.lookahead = float(lookback), float(lookahead)
         # dispatch: longest-expected-first by the previous tick's iteration counts of the same vehicles
@@ -154,8 +178,13 @@ class ClosedLoop:
         # plant step with the simulator's command throttle - brake (models/Model.py:83-88)
         self.cmd[0] = self.cmd_throttle - self.cmd_brake
         self.cmd[1] = self.cmd_steer
-        self._check(self.lib.mr_plant_step(self.plant, B, _ptr(self.state), _ptr(self.cmd), self.dt,
-                                           _ptr(self.state_next), sp))
+        if self.learned is None:
+            self._check(self.lib.mr_plant_step(self.plant, B, _ptr(self.state), _ptr(self.cmd), self.dt,
+                                               _ptr(self.state_next), sp))
+        else:
+            L = self.learned
+            self._check(self.lib.mr_vehicle_step(ctypes.byref(L["cfg"]), B, _ptr(self.state), _ptr(self.cmd), self.dt,
+                                                 L["P"], _ptr(L["params"]), _ptr(L["Fz"]), _ptr(self.state_next), sp))
         self.state, self.state_next = self.state_next, self.state
         self.old_yaw = yaw.clone()
         self.prev_progress = self.progress.clone()
@@ -172,5 +201,4 @@ class ClosedLoop:
 
 
 def ctypes_stream(st):
-    import ctypes
     return ctypes.c_void_p(st.cuda_stream)

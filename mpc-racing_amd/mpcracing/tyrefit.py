@@ -186,6 +186,15 @@ class FitResult:
             raise ValueError("Pacejka fits feed BatchSolver(tyres=result.tyres)")
         return {"Cf": float(self.params[0]), "Cr": float(self.params[1])}
 
+    def rank_by_rollout(self, log, horizon, **kw):
+        """Run indices ordered by the position RMSE of their best parameters at step ``horizon`` of open-loop
+        rollouts from every admissible row of ``log`` [9][T] (``mpcracing.rollout.load_log``), best first;
+        runs without a finite value last.  The errors are kept as ``.rollout`` (a RolloutErrors)."""
+        from .rollout import rollout_errors
+        self.rollout = rollout_errors(log, self, horizon=horizon, **kw)
+        rmse = self.rollout.position_rmse()
+        return np.argsort(np.where(np.isfinite(rmse), rmse, np.inf), kind="stable")
+
     def state_dict(self):
         """The reference model's state dict (torch fp64 tensors; ``torch.save`` of it loads in its tooling)."""
         import torch

@@ -9,6 +9,7 @@ bounds of mpcracing.hip): variants/lib_<name>.so, run by tools/gpu_flags_ab.sh o
   nofma    no floating-point contraction (-ffp-contract=off: the host build's arithmetic, no FMA)
   inline   the sweeps force-inlined into the solve kernel (MR_SWEEP_INLINE: one register allocation, no call ABI)
   wspad    64 Ki unused words after each instance's workspace (an out-of-range write would land there)
+  rollout_nostats  the rollout kernel with its per-step reductions compiled out (MR_ROLLOUT_STATS=0; tools/rollout_bench.py)
   poisonP  LDS and workspace filled with pattern P (1 NaN, 2 zero, 3 -1e30) at kernel start (determinism_probe.py)
 """
 import os
@@ -32,6 +33,7 @@ VARIANTS = {
     "poison3": DEFAULT_FLAGS + ["-DMR_POISON=3"],
     "inline": DEFAULT_FLAGS + ["-DMR_SWEEP_INLINE=1"],
     "wspad": DEFAULT_FLAGS + ["-DMR_WS_PAD=65536"],
+    "rollout_nostats": DEFAULT_FLAGS + ["-DMR_ROLLOUT_STATS=0"],
 }
 
 
