@@ -36,7 +36,7 @@ extern "C" {
    a caller built against another header can refuse to run (101: mr_config.dispatch_order,
    mr_outputs.lam_g / timeline, mr_config without lane_penalty (hard lane rows), status 4 = infeasible;
    102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
-   mr_vehicle_step, mr_tyre_rollout) */
+   mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -330,6 +330,36 @@ int mr_vehicle_step(const mr_tyrefit_config* cfg, int32_t n, const double* state
 int mr_tyre_rollout(const mr_tyrefit_config* cfg, int32_t T, const double* log, int32_t n_start, const int32_t* start,
                     int32_t H, int32_t P, const double* params, const double* Fz, double* stats, int32_t* count,
                     double* pred, void* hip_stream);
+
+/* ---- the models/ plant with run-time parameters and its rollouts (csrc/mr_plant.h, mr_plantroll.h) ------
+ * How well does the plant of the closed loop reproduce a logged drive, and which constants would do better:
+ * script/verify_kinematic.py:24-41, verify_dynamic.py:26-43 and verify_blend.py:24-41 (a models/ plant rolled
+ * along a drive), script/test_model_error.py (per-component error statistics) and script/optimize_coeffs.py
+ * (a search over dt or (Cf, Cr) by serial rollouts).  A parameter set is MR_PLANT_NPAR doubles: the fields of
+ * models/VehicleParameters.py:8-38 that the plant reads, in the order m, max_steer, T_max, r_wheel, C_wheel, R,
+ * rho, C_d, A_f, C_roll, regen_brake_accel, Iz, lf, lr, Cf, Cr, g, Vblendmin, Vblendmax, then the penalty term
+ * of Model.Fx (models/Model.py:50): amplitude factor (1), location (0.5), width (0.0775).  All arrays but
+ * mr_plant_params_default's are caller-owned DEVICE pointers. */
+#define MR_PLANT_NPAR 22
+
+/* The class defaults of models/VehicleParameters.py:8-38 and of models/Model.py:50 (host pointer).  With
+   this vector the two entries below compute bitwise what mr_plant_step computes. */
+int mr_plant_params_default(double* params /* [MR_PLANT_NPAR] */);
+/* mr_plant_step with parameters params [P][MR_PLANT_NPAR]: shared (P == 1) or one vector per vehicle (P == n).
+   Model.step(throttle_cmd, steer_cmd, dt) with model.params set (models/Model.py:83-88; the Cf / Cr arguments of
+   models/DynamicBicycleModel.py:16-28).  out may alias state.  Runs on the device that owns `state`. */
+int mr_plant_step_params(int32_t model, int32_t n, const double* state, const double* cmd, double dt, int32_t P,
+                         const double* params, double* out, void* hip_stream); /* P == 1 or P == n */
+/* Rollouts of P parameter sets of plant `model` (MR_PLANT_*) along log [9][T] (the layout of mr_tyre_rollout),
+   replacing the loops of script/verify_kinematic.py:39-41, verify_dynamic.py:41-43, verify_blend.py:39-41 and
+   the objective of script/optimize_coeffs.py:34-48: x_0 = log[0..5][s], x_k = step(x_{k-1}, throttle[s+k-1],
+   steer[s+k-1], dt_k), dt_k = ts[s+k], or dt[p] for every step of set p when dt is not NULL (MR_ERR_ARG if an
+   entry is not a positive finite number).  Error e = log[0..5][s+k] - x_k; the yaw error is the wrapped
+   difference atan2(sin d, cos d) (the plant wraps its yaw, the log's is continuous).  stats, count, pred, the
+   stopping of non-finite rollouts, the start check and the synchronisation are those of mr_tyre_rollout. */
+int mr_plant_rollout(int32_t model, int32_t T, const double* log, int32_t n_start, const int32_t* start, int32_t H,
+                     int32_t P, const double* params, const double* dt /* [P] or NULL */, double* stats,
+                     int32_t* count, double* pred, void* hip_stream);
 
 #ifdef __cplusplus
 }

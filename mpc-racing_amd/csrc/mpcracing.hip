@@ -18,6 +18,7 @@
 #include "mr_plant.h"
 #include "mr_tyrefit.h"
 #include "mr_rollout.h"
+#include "mr_plantroll.h"
 #include <vector>
 
 using namespace mr;
@@ -546,6 +547,29 @@ __global__ __launch_bounds__(kTrackBlock) void vehicle_step_kernel(mr_tyrefit_co
   ro_vehicle_step<KIND>(cfg, n, i, state, cmd, dt, P, params, Fz, out);
 }
 
+// checking pass of mr_plant_rollout: *bad = 1 when any fixed step is not a positive finite number
+__global__ __launch_bounds__(256) void plant_dt_check_kernel(const double* dt, int P, int* bad) {
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < P; k += (int64_t)gridDim.x * 256)
+    if (!plant_dt_ok(dt[k])) *bad = 1;
+}
+// Plant rollouts (mr_plantroll.h): the launch shape of tyre_rollout_kernel, one instantiation per model; the
+// finishing kernel and the start check are tyre_rollout_finish_kernel and tyre_start_check_kernel.  The blended
+// model needs the whole register file of 1 wave per SIMD (256 VGPRs + 10 AGPRs, no scratch).
+template <int MODEL>
+__global__ __launch_bounds__(64, 1) void plant_rollout_kernel(PrArgs A, int p0) {
+  __shared__ double lds[RO_LDS_WORDS];
+  Wv w{(int)threadIdx.x};
+  const int pl = (int)(blockIdx.x / A.n_chunk), chunk = (int)(blockIdx.x % A.n_chunk);
+  pr_chunk<MODEL>(A, p0 + pl, pl, chunk, lds, w);
+}
+__global__ __launch_bounds__(kTrackBlock) void plant_step_params_kernel(int model, int n, const double* state,
+                                                                        const double* cmd, double dt, int P,
+                                                                        const double* params, double* out) {
+  const int i = blockIdx.x * kTrackBlock + threadIdx.x;
+  if (i >= n) return;
+  pr_vehicle_step(model, n, i, state, cmd, dt, P, params, out);
+}
+
 extern "C" {
 
 int mr_version(void) { return MR_ABI_VERSION; }
@@ -971,6 +995,90 @@ int mr_tyre_rollout(const mr_tyrefit_config* cfg, int32_t T, const double* log, 
   for (int64_t p0 = 0; p0 < P && el == hipSuccess; p0 += P_launch) {
     const int Pl = (int)(P - p0 < P_launch ? P - p0 : P_launch);
     hipLaunchKernelGGL(tyre_rollout_kernel, dim3((unsigned)((int64_t)Pl * A.n_chunk)), dim3(64), 0, st, A, (int)p0);
+    hipLaunchKernelGGL(tyre_rollout_finish_kernel, dim3((unsigned)(((int64_t)Pl * H + 63) / 64)), dim3(64), 0, st,
+                       (int)H, A.n_chunk, (const double*)A.partials, (int)p0, Pl, stats, count);
+    el = hipGetLastError();
+  }
+  hipError_t es = hipStreamSynchronize(st);  // the partials buffer is released below
+  (void)hipFree(A.partials);
+  HIP_TRY(el);
+  HIP_TRY(es);
+  return MR_OK;
+}
+
+int mr_plant_params_default(double* params) {
+  if (!params) return fail(MR_ERR_ARG, "null argument");
+  plant_params_default(params);
+  return MR_OK;
+}
+
+int mr_plant_step_params(int32_t model, int32_t n, const double* state, const double* cmd, double dt, int32_t P,
+                         const double* params, double* out, void* hip_stream) {
+  if (const char* e = plant_step_params_check(model, n, P)) return fail(MR_ERR_ARG, e);
+  if (!state || !cmd || !params || !out) return fail(MR_ERR_ARG, "null argument");
+  if (n == 0) return MR_OK;
+  int dev = -1;
+  if (pointer_device(state, &dev) != 0) return fail(MR_ERR_ARG, "state is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  hipLaunchKernelGGL(plant_step_params_kernel, dim3((n + kTrackBlock - 1) / kTrackBlock), dim3(kTrackBlock), 0,
+                     (hipStream_t)hip_stream, (int)model, (int)n, state, cmd, dt, (int)P, params, out);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_plant_rollout(int32_t model, int32_t T, const double* log, int32_t n_start, const int32_t* start, int32_t H,
+                     int32_t P, const double* params, const double* dt, double* stats, int32_t* count, double* pred,
+                     void* hip_stream) {
+  if (const char* e = plant_rollout_check(model, T, n_start, H, P)) return fail(MR_ERR_ARG, e);
+  if (!log || !start || !params || !stats || !count) return fail(MR_ERR_ARG, "null argument");
+  int dev = -1;
+  if (pointer_device(log, &dev) != 0) return fail(MR_ERR_ARG, "log is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  hipStream_t st = (hipStream_t)hip_stream;
+  // checking pass: no start is used as a row index before it is known to be in range, and every fixed
+  // step is a positive finite number
+  int* bad_dev = nullptr;
+  int bad[2] = {0, 0};
+  HIP_TRY(hipMalloc(&bad_dev, 2 * sizeof(int)));
+  hipError_t e0 = hipMemsetAsync(bad_dev, 0, 2 * sizeof(int), st);
+  const int blocks = (n_start + 255) / 256;
+  hipLaunchKernelGGL(tyre_start_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, start,
+                     (int)n_start, (int)(T - 1 - H), bad_dev);
+  if (dt) {
+    const int bd = (P + 255) / 256;
+    hipLaunchKernelGGL(plant_dt_check_kernel, dim3((unsigned)(bd < 4096 ? bd : 4096)), dim3(256), 0, st, dt, (int)P,
+                       bad_dev + 1);
+  }
+  hipError_t e1 = hipGetLastError();
+  hipError_t e2 = hipMemcpyAsync(bad, bad_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+  hipError_t e3 = hipStreamSynchronize(st);
+  (void)hipFree(bad_dev);
+  HIP_TRY(e0);
+  HIP_TRY(e1);
+  HIP_TRY(e2);
+  HIP_TRY(e3);
+  if (bad[0]) return fail(MR_ERR_ARG, "start entry out of range [0, T - 1 - H]");
+  if (bad[1]) return fail(MR_ERR_ARG, "dt entry not a positive finite number");
+  PrArgs A;
+  A.T = T; A.n_start = n_start; A.H = H;
+  A.n_chunk = (n_start + WL - 1) / WL;
+  A.log = log; A.start = start; A.params = params; A.dt = dt; A.pred = pred;
+  // the partials of at most P_launch sets at a time (256 MiB): launches on one stream reuse the buffer in order
+  const int64_t per_set = (int64_t)A.n_chunk * H * RO_NPART * (int64_t)sizeof(double);
+  int64_t P_launch = ((int64_t)256 << 20) / per_set;
+  if (P_launch < 1) P_launch = 1;
+  if (P_launch > P) P_launch = P;
+  HIP_TRY(hipMalloc(&A.partials, (size_t)(per_set * P_launch)));
+  hipError_t el = hipSuccess;
+  for (int64_t p0 = 0; p0 < P && el == hipSuccess; p0 += P_launch) {
+    const int Pl = (int)(P - p0 < P_launch ? P - p0 : P_launch);
+    const dim3 grid((unsigned)((int64_t)Pl * A.n_chunk));
+    if (model == MR_PLANT_KINEMATIC)
+      hipLaunchKernelGGL(plant_rollout_kernel<PLANT_KIN>, grid, dim3(64), 0, st, A, (int)p0);
+    else if (model == MR_PLANT_DYNAMIC)
+      hipLaunchKernelGGL(plant_rollout_kernel<PLANT_DYN>, grid, dim3(64), 0, st, A, (int)p0);
+    else
+      hipLaunchKernelGGL(plant_rollout_kernel<PLANT_BLEND>, grid, dim3(64), 0, st, A, (int)p0);
     hipLaunchKernelGGL(tyre_rollout_finish_kernel, dim3((unsigned)(((int64_t)Pl * H + 63) / 64)), dim3(64), 0, st,
                        (int)H, A.n_chunk, (const double*)A.partials, (int)p0, Pl, stats, count);
     el = hipGetLastError();

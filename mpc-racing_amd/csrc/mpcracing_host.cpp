@@ -14,6 +14,7 @@
 #include "mr_plant.h"
 #include "mr_tyrefit.h"
 #include "mr_rollout.h"
+#include "mr_plantroll.h"
 
 using namespace mr;
 
@@ -385,6 +386,61 @@ int mrh_tyre_rollout(const mr_tyrefit_config* cfg, int T, const double* log, int
     RolloutJob job{&A, (int)(b / A.n_chunk), (int)(b % A.n_chunk), lds.data()};
     HostWave* hw = new HostWave();
     host_wave_run(*hw, &rollout_body, &job);
+    delete hw;
+  }
+  for (int p = 0; p < P; ++p)
+    for (int k = 0; k < H; ++k) ro_finish(H, A.n_chunk, partials.data(), p, p, k, stats, count);
+  return 0;
+}
+
+// ---- the plant with run-time parameters and its rollouts (mr_plantroll.h) ----
+int mrh_plant_params_default(double* params) {
+  plant_params_default(params);
+  return 0;
+}
+int mrh_plant_step_params(int model, int n, const double* state, const double* cmd, double dt, int P,
+                          const double* params, double* out) {
+  if (const char* e = plant_step_params_check(model, n, P)) return tyrefit_fail(e);
+  if (!state || !cmd || !params || !out) return tyrefit_fail("null argument");
+  for (int i = 0; i < n; ++i) pr_vehicle_step(model, n, i, state, cmd, dt, P, params, out);
+  return 0;
+}
+
+struct PlantRolloutJob {
+  const PrArgs* A;
+  int model, p, chunk;
+  double* lds;
+};
+static void plant_rollout_body(HostWave* hw, int lane, void* arg) {
+  PlantRolloutJob* j = (PlantRolloutJob*)arg;
+  Wv w{lane, hw};
+  if (j->model == PLANT_KIN) pr_chunk<PLANT_KIN>(*j->A, j->p, j->p, j->chunk, j->lds, w);
+  else if (j->model == PLANT_DYN) pr_chunk<PLANT_DYN>(*j->A, j->p, j->p, j->chunk, j->lds, w);
+  else pr_chunk<PLANT_BLEND>(*j->A, j->p, j->p, j->chunk, j->lds, w);
+  wsync(w);
+}
+int mrh_plant_rollout(int model, int T, const double* log, int n_start, const int32_t* start, int H, int P,
+                      const double* params, const double* dt, double* stats, int32_t* count, double* pred,
+                      int nthreads) {
+  if (const char* e = plant_rollout_check(model, T, n_start, H, P)) return tyrefit_fail(e);
+  if (!log || !start || !params || !stats || !count) return tyrefit_fail("null argument");
+  for (int k = 0; k < n_start; ++k)
+    if (start[k] < 0 || start[k] > T - 1 - H) return tyrefit_fail("start entry out of range [0, T - 1 - H]");
+  for (int p = 0; dt && p < P; ++p)
+    if (!plant_dt_ok(dt[p])) return tyrefit_fail("dt entry not a positive finite number");
+  PrArgs A;
+  A.T = T; A.n_start = n_start; A.H = H;
+  A.n_chunk = (n_start + WL - 1) / WL;
+  A.log = log; A.start = start; A.params = params; A.dt = dt; A.pred = pred;
+  std::vector<double> partials((size_t)P * A.n_chunk * H * RO_NPART, NAN);
+  A.partials = partials.data();
+  const int64_t jobs = (int64_t)P * A.n_chunk;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int64_t b = 0; b < jobs; ++b) {
+    std::vector<double> lds((size_t)RO_LDS_WORDS, NAN);
+    PlantRolloutJob job{&A, model, (int)(b / A.n_chunk), (int)(b % A.n_chunk), lds.data()};
+    HostWave* hw = new HostWave();
+    host_wave_run(*hw, &plant_rollout_body, &job);
     delete hw;
   }
   for (int p = 0; p < P; ++p)

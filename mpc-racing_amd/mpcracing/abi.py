@@ -11,6 +11,8 @@ ABI_VERSION = 103  # MR_ABI_VERSION of include/mpcracing.h
 MR_MODEL = {"kin": 0, "dyn": 1, "blend": 2, "blend_pacejka": 3, "dyn_pacejka": 4}
 MR_PREC = {"fp64": 0, "fp32": 1}
 MR_TYRE = {"linear": 0, "pacejka": 1}
+MR_PLANT = {"kin": 0, "dyn": 1, "blend": 2}
+MR_PLANT_NPAR = 22  # include/mpcracing.h
 MR_OPT = {"sgd": 0, "adam": 1, "adamw": 2}
 STATUS = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "failed", 4: "infeasible"}
 
@@ -56,7 +58,8 @@ EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_
            "mr_track_create", "mr_track_destroy", "mr_track_eval", "mr_track_frame", "mr_track_error_sign",
            "mr_track_polyfit", "mr_track_polyfit_deg", "mr_track_lookup_error", "mr_track_projection", "mr_track_prep",
            "mr_spline_from_waypoints", "mr_track_lane_table", "mr_agent_sense", "mr_plant_step",
-           "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout"]
+           "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout",
+           "mr_plant_params_default", "mr_plant_step_params", "mr_plant_rollout"]
 
 
 def _bind_product(lib):
@@ -92,6 +95,9 @@ def _bind_product(lib):
     lib.mr_tyre_fit.argtypes = [TC, _I32, V, _I32, V, _I32, V, V, V, V, ctypes.c_int64, V, V, V, V, V, V, V, V]
     lib.mr_vehicle_step.argtypes = [TC, _I32, V, V, _D, _I32, V, V, V, V]
     lib.mr_tyre_rollout.argtypes = [TC, _I32, V, _I32, V, _I32, _I32, V, V, V, V, V, V]
+    lib.mr_plant_params_default.argtypes = [_PD]
+    lib.mr_plant_step_params.argtypes = [_I32, _I32, V, V, _D, _I32, V, V, V]
+    lib.mr_plant_rollout.argtypes = [_I32, _I32, V, _I32, V, _I32, _I32, V, V, V, V, V, V]
     return lib
 
 
@@ -144,5 +150,8 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_tyrefit_last_error.restype = ctypes.c_char_p
     lib.mrh_vehicle_step.argtypes = [TC, I, V, V, _D, I, V, V, V]
     lib.mrh_tyre_rollout.argtypes = [TC, I, V, I, V, I, I, V, V, V, V, V, I]
+    lib.mrh_plant_params_default.argtypes = [_PD]
+    lib.mrh_plant_step_params.argtypes = [I, I, V, V, _D, I, V, V]
+    lib.mrh_plant_rollout.argtypes = [I, I, V, I, V, I, I, V, V, V, V, V, I]
     lib.mrh_pacejka_dparams.argtypes = [_PD, _D, _D, _PD, _PD]
     return lib

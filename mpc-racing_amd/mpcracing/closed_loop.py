@@ -16,7 +16,8 @@ Here every tick is four device steps on one stream, with no host synchronisation
 4. ``mr_plant_step``   (csrc/mr_plant.h)  one plant step per vehicle with the applied command
    (``plant="learned"``: ``mr_vehicle_step``, csrc/mr_rollout.h -- the one-step model of the tyre fit,
    learning/vehicle.py:136-205, with ``plant_tyres``: the model-matched plant of an MPC that carries the
-   same learned tyres).
+   same learned tyres; ``plant_params``: ``mr_plant_step_params``, the same models/ plant with run-time
+   constants, one vector or one per vehicle).
 
 Measurement model: the plant state is the simulator truth; the agent's own derivations are kept
 -- yaw rate by finite differences of the (wrapped) yaw over the tick (agent.py:240-249), the
@@ -43,7 +44,7 @@ class ClosedLoop:
     def __init__(self, track="shanghai_intl_circuit", B=1, N=15, plant="blend", mpc_model="dyn",
                  precision="fp64", Ts=0.05, dt=0.05, start_control_at=50, lookback=5.0, lookahead=45.0,
                  runtime=(1000.0, 0.85, 50.0, 2.0, 5000.0), device=0, plant_tyres=None, plant_kind=None,
-                 **solver_kw):
+                 plant_params=None, **solver_kw):
         if start_control_at < 1:
             raise ValueError("start_control_at >= 1: the MPC's yaw rate is a finite difference over one tick")
         self.track = track if isinstance(track, DeviceTrack) else DeviceTrack(track, device=device)
@@ -51,6 +52,17 @@ class ClosedLoop:
         self.dev = self.track.device
         self.B, self.N = int(B), int(N)
         self.learned = None
+        self.plant_params = None
+        if plant_params is not None:
+            # one vector [MR_PLANT_NPAR] (rollout.plant_params) or one per vehicle [B][MR_PLANT_NPAR]
+            from . import abi
+            if plant == "learned":
+                raise ValueError('plant_params goes with plant="kin", "dyn" or "blend"')
+            q = np.atleast_2d(np.asarray(plant_params, dtype=np.float64))
+            if q.ndim != 2 or q.shape[1] != abi.MR_PLANT_NPAR or q.shape[0] not in (1, self.B):
+                raise ValueError(f"plant_params: [{abi.MR_PLANT_NPAR}] or [{self.B}][{abi.MR_PLANT_NPAR}], "
+                                 f"got {q.shape}")
+            self.plant_params = torch.as_tensor(q, dtype=torch.float64, device=self.dev).contiguous()
         if plant == "learned":
             # plant_tyres: a FitResult (its best run) or (params [n_par] or [B][n_par], Fz or None) with plant_kind
             from . import rollout, tyrefit
@@ -178,7 +190,11 @@ class ClosedLoop:
         # plant step with the simulator's command throttle - brake (models/Model.py:83-88)
         self.cmd[0] = self.cmd_throttle - self.cmd_brake
         self.cmd[1] = self.cmd_steer
-        if self.learned is None:
+        if self.plant_params is not None:
+            q = self.plant_params
+            self._check(self.lib.mr_plant_step_params(self.plant, B, _ptr(self.state), _ptr(self.cmd), self.dt,
+                                                      q.shape[0], _ptr(q), _ptr(self.state_next), sp))
+        elif self.learned is None:
             self._check(self.lib.mr_plant_step(self.plant, B, _ptr(self.state), _ptr(self.cmd), self.dt,
                                                _ptr(self.state_next), sp))
         else:

@@ -7,6 +7,10 @@ in one call of ``mr_tyre_rollout`` (csrc/mr_rollout.h: one 64-lane wavefront per
 64 starts, fixed butterfly reductions, bitwise repeatable); ``vehicle_step`` is one step of the same model
 for a batch of vehicles (``mr_vehicle_step``), the plant of ``ClosedLoop(plant="learned")``.
 
+``plant_rollout_errors`` / ``plant_step`` / ``plant_params`` are the same for the ``models/`` plant of the closed
+loop with its constants as data (``mr_plant_rollout``, ``mr_plant_step_params``, csrc/mr_plantroll.h;
+script/verify_kinematic.py, verify_dynamic.py, verify_blend.py); ``mpcracing.plantfit`` searches them.
+
 ``host_twin=True`` runs the g++ build of the same source instead (TEST-ONLY, explicit; there is no
 fallback: without it a missing GPU or library is an error).
 """
@@ -91,6 +95,14 @@ class RolloutErrors:
         with np.errstate(invalid="ignore", divide="ignore"):
             return np.where(n > 0, np.sqrt((self.sumsq[:, k, 0] + self.sumsq[:, k, 1]) / n), np.nan)
 
+    def position_cost(self):
+        """[P]: the sum over the steps of sumsq_X + sumsq_Y, added in step order.  For one start this is the
+        square of script/optimize_coeffs.py:34-38's ``_cost`` (numpy.linalg.norm of the position differences)."""
+        cost = np.zeros(self.sumsq.shape[0])
+        for k in range(self.horizon):
+            cost = cost + (self.sumsq[:, k, 0] + self.sumsq[:, k, 1])
+        return cost
+
 
 def rollout_errors(log, tyres, kind=None, horizon=10, starts=None, keep_pred=False, device=0, host_twin=False,
                    **vehicle):
@@ -139,5 +151,89 @@ def vehicle_step(state, cmd, dt, tyres, kind=None, device=0, host_twin=False, **
         be.check(be.lib.mrh_vehicle_step(*args))
     else:
         be.check(be.lib.mr_vehicle_step(*args, be.stream()))
+        be.torch.cuda.synchronize(be.dev)
+    return be.get(out)
+
+
+# ---- the models/ plant with run-time parameters (csrc/mr_plant.h, mr_plantroll.h) ----
+PLANT_FIELDS = ["m", "max_steer", "T_max", "r_wheel", "C_wheel", "R", "rho", "C_d", "A_f", "C_roll",
+                "regen_brake_accel", "Iz", "lf", "lr", "Cf", "Cr", "g", "Vblendmin", "Vblendmax",
+                "penalty_amp", "penalty_loc", "penalty_width"]
+# models/VehicleParameters.py:8-38 and models/Model.py:50; the libraries' mr_plant_params_default gives the same
+# vector (tests/plantroll_cases.py)
+PLANT_DEFAULTS = [1845.0, 70.0, 743.0, 0.37, 2 * 3.14 * 0.37, 9.0, 1.225, 0.23, 2.2, 0.012, 0.2, 3960.0, 0.8, 2.0,
+                  65000.0, 65000.0, 9.81, 2.0, 15.0, 1.0, 0.5, 0.0775]
+assert len(PLANT_FIELDS) == len(PLANT_DEFAULTS) == abi.MR_PLANT_NPAR
+
+
+def plant_params(**overrides):
+    """[MR_PLANT_NPAR]: the plant's default parameters (the class defaults of models/VehicleParameters.py and
+    the penalty term of Model.Fx, as ``mr_plant_params_default``) with ``overrides`` by field name
+    (``PLANT_FIELDS``); an unknown name raises."""
+    unknown = [k for k in overrides if k not in PLANT_FIELDS]
+    if unknown:
+        raise ValueError(f"unknown plant parameter(s) {unknown}; the fields are {PLANT_FIELDS}")
+    q = np.array(PLANT_DEFAULTS, np.float64)
+    for k, v in overrides.items():
+        q[PLANT_FIELDS.index(k)] = float(v)
+    return q
+
+
+def _plant_args(model, params):
+    if model not in abi.MR_PLANT:
+        raise ValueError(f"unknown plant model {model!r} (kin, dyn, blend)")
+    params = plant_params() if params is None else np.asarray(params, np.float64)
+    params = np.ascontiguousarray(np.atleast_2d(params))
+    if params.ndim != 2 or params.shape[1] != abi.MR_PLANT_NPAR or params.shape[0] < 1:
+        raise ValueError(f"params: expected [P][{abi.MR_PLANT_NPAR}] with P >= 1, got {params.shape}")
+    return abi.MR_PLANT[model], params
+
+
+def plant_rollout_errors(log, model, params=None, dt=None, horizon=10, starts=None, keep_pred=False, device=0,
+                         host_twin=False):
+    """Roll the ``model`` plant ("kin", "dyn", "blend") with ``params`` [P][MR_PLANT_NPAR] (``plant_params``;
+    default: one default set) forward ``horizon`` steps from every start row of ``log`` [9][T] and reduce truth
+    minus prediction (the yaw error wrapped to (-pi, pi]).  The step length is the log's ``ts`` or, with ``dt``
+    (a number or [P]), one fixed step per set.  One ``mr_plant_rollout`` call; returns a RolloutErrors."""
+    log = np.ascontiguousarray(log, np.float64)
+    if log.ndim != 2 or log.shape[0] != 9:
+        raise ValueError(f"log: expected [9][T], got {log.shape}")
+    model, params = _plant_args(model, params)
+    T, H, P = log.shape[1], int(horizon), params.shape[0]
+    if H < 1 or H > T - 1:
+        raise ValueError(f"horizon {H} outside [1, T - 1 = {T - 1}]")
+    starts = np.arange(T - H, dtype=np.int32) if starts is None else np.ascontiguousarray(starts, np.int32).ravel()
+    n = len(starts)
+    if dt is not None:
+        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (P,)))
+    be = _Host() if host_twin else _Device(device)
+    d = [be.put(log), be.put(starts), be.put(params)] + ([be.put(dt)] if dt is not None else [])
+    stats, count = be.empty((P, H, 6, 4)), be.empty((P, H), np.int32)
+    pred = be.empty((P, H, 6, n)) if keep_pred else None
+    args = [model, T, be.ptr(d[0]), n, be.ptr(d[1]), H, P, be.ptr(d[2]), be.ptr(d[3]) if dt is not None else None,
+            be.ptr(stats), be.ptr(count), be.ptr(pred) if keep_pred else None]
+    if host_twin:
+        be.check(be.lib.mrh_plant_rollout(*args, 16))
+    else:
+        be.check(be.lib.mr_plant_rollout(*args, be.stream()))
+        be.torch.cuda.synchronize(be.dev)
+    return RolloutErrors(be.get(stats), be.get(count), be.get(pred) if keep_pred else None, starts, H)
+
+
+def plant_step(state, cmd, dt, model, params=None, device=0, host_twin=False):
+    """One plant step of n vehicles: state [6][n], cmd [2][n] = (throttle - brake, steer) -> [6][n] (numpy).
+    params: one vector shared by all vehicles (default: the defaults) or one per vehicle ([n][MR_PLANT_NPAR])."""
+    state = np.ascontiguousarray(state, np.float64).reshape(6, -1)
+    n = state.shape[1]
+    cmd = np.ascontiguousarray(cmd, np.float64).reshape(2, n)
+    model, params = _plant_args(model, params)
+    be = _Host() if host_twin else _Device(device)
+    d = [be.put(state), be.put(cmd), be.put(params)]
+    out = be.empty((6, n))
+    args = [model, n, be.ptr(d[0]), be.ptr(d[1]), float(dt), params.shape[0], be.ptr(d[2]), be.ptr(out)]
+    if host_twin:
+        be.check(be.lib.mrh_plant_step_params(*args))
+    else:
+        be.check(be.lib.mr_plant_step_params(*args, be.stream()))
         be.torch.cuda.synchronize(be.dev)
     return be.get(out)
