@@ -36,7 +36,8 @@ extern "C" {
    a caller built against another header can refuse to run (101: mr_config.dispatch_order,
    mr_outputs.lam_g / timeline, mr_config without lane_penalty (hard lane rows), status 4 = infeasible;
    102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
-   mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout) */
+   mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout,
+   mr_pid_gains_default, mr_pid_control, mr_pid_drive) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -360,6 +361,40 @@ int mr_plant_step_params(int32_t model, int32_t n, const double* state, const do
 int mr_plant_rollout(int32_t model, int32_t T, const double* log, int32_t n_start, const int32_t* start, int32_t H,
                      int32_t P, const double* params, const double* dt /* [P] or NULL */, double* stats,
                      int32_t* count, double* pred, void* hip_stream);
+
+/* ---- the PID agent and whole drives of it against the models/ plant (csrc/mr_pid.h) ---------------------
+ * agent_pid.py, the controller that produced the logs the reference learns from: pure pursuit plus PD on the
+ * centerline error (get_alpha / pp_delta :95-124, :211-215), a curvature-based speed target (get_target_vel
+ * :126-131) with PD throttle and a brake floor of 0.5 (:217-226).  All arrays but mr_pid_gains_default's are
+ * caller-owned DEVICE pointers on the track's device. */
+#define MR_PID_NGAIN 8
+#define MR_PID_NMEM 4
+#define MR_PID_NOUT 8
+#define MR_PID_NLOG 14 /* X, Y, yaw, vx, vy, yawdot (plant state), yawdot_fd, progress, error,
+                          cmd_throttle, cmd_steer, cmd_brake, target_vel, kappa */
+/* The tunable parameters of agent_pid.py:47-58 (host pointer): k, zeta, kP_steer, kD_steer, kP_throttle,
+   kD_throttle, lookahead, vel_lookahead_factor = 1.1, 15, 0.1, 0.1, 0.82954, 1.21341, 3.0, 40. */
+int mr_pid_gains_default(double* gains /* host, [MR_PID_NGAIN] */);
+/* One Agent.run_step (agent_pid.py:157-237) for n vehicles: state [6][n] = (X, Y, yaw, vx, vy, yawdot) with
+   body-frame velocities; mem [4][n] in/out = (prev_progress, last_error, last_throttle_error, old_yaw), NaN for
+   the reference's None (first tick: global projection, yawdot_fd NaN); gains [G][8] (G == 1 or n);
+   out [8][n] = (progress, error, cmd_throttle, cmd_steer, cmd_brake, target_vel, kappa, yawdot_fd), yawdot_fd
+   the finite difference of :163-172 over dt.  One addition to the reference: cmd_steer is clamped to [-1, 1]
+   (the range of carla.VehicleControl.steer); last_error takes the unclamped law's error.  Tracks without lane
+   tables are fine. */
+int mr_pid_control(const mr_track* tr, int32_t n, const double* state, double* mem, int32_t G,
+                   const double* gains, double dt, double* out, void* hip_stream);
+/* T ticks of agent + plant in one launch, replacing the CARLA loop around agent_pid.Agent.run_step with
+   Model.step(cmd_throttle - cmd_brake, cmd_steer, dt) of plant `model` (MR_PLANT_*).  state [6][n] and mem [4][n]
+   are in/out (a second call continues the drive); params [P][MR_PLANT_NPAR] (P == 1 or n); log: rows of
+   MR_PID_NLOG selected by log_mask (bit r = row r), packed in row order, [popcount(log_mask)][T][n], NULL with
+   log_mask 0 for none; ticks_done [n].  A vehicle whose state or command is not finite at a tick, or whose
+   plant step is not, stops before that tick: its rows from there on are NaN, state and mem keep the values
+   the tick started from, ticks_done is the number of ticks before it; the other vehicles do not change.
+   1 <= T <= 4096 (longer drives are several calls); dt positive and finite. */
+int mr_pid_drive(const mr_track* tr, int32_t model, int32_t n, int32_t T, double dt, double* state, double* mem,
+                 int32_t G, const double* gains, int32_t P, const double* params, uint32_t log_mask, double* log,
+                 int32_t* ticks_done, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 #include "mr_tyrefit.h"
 #include "mr_rollout.h"
 #include "mr_plantroll.h"
+#include "mr_pid.h"
 #include <vector>
 
 using namespace mr;
@@ -570,6 +571,37 @@ __global__ __launch_bounds__(kTrackBlock) void plant_step_params_kernel(int mode
   pr_vehicle_step(model, n, i, state, cmd, dt, P, params, out);
 }
 
+// The PID agent (mr_pid.h).  One tick: one lane per vehicle, like the other centerline kernels.
+__global__ __launch_bounds__(kTrackBlock) void pid_control_kernel(TrackView T, int n, const double* state, double* mem,
+                                                                  int G, const double* gains, double dt, double* out) {
+  const int i = blockIdx.x * kTrackBlock + threadIdx.x;
+  if (i >= n) return;
+  pid_control_vehicle(T, n, i, state, mem, G, gains, dt, out);
+}
+// A whole drive in one launch: one lane per vehicle, one wavefront per workgroup, T ticks of agent + plant with
+// state, memory and gains in registers.  SHARED: one parameter vector for all vehicles, read from a
+// lane-invariant address before the loop (scalar loads, the vector in SGPRs as in plant_rollout_kernel);
+// otherwise every lane loads its own.  The loop ends early only when every lane of the wave has stopped.
+struct PidVoteWave {
+  __device__ __forceinline__ bool operator()(bool alive) const { return __builtin_amdgcn_ballot_w64(alive) != 0; }
+};
+template <int MODEL, bool SHARED>
+__global__ __launch_bounds__(64) void pid_drive_kernel(TrackView T, PidDriveArgs A) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const bool active = i < A.n;
+  double q[MR_PLANT_NPAR];
+  const double* src = A.params + (SHARED ? (int64_t)0 : (int64_t)(active ? i : 0) * MR_PLANT_NPAR);
+  for (int j = 0; j < MR_PLANT_NPAR; ++j) q[j] = src[j];
+  pid_drive_vehicle<MODEL>(T, A, i, active, q, PidVoteWave());
+}
+
+template <int MODEL>
+static void pid_drive_launch(const mr_track* tr, const PidDriveArgs& A, hipStream_t st) {
+  const dim3 grid((unsigned)((A.n + 63) / 64)), block(64);
+  if (A.P == 1) hipLaunchKernelGGL((pid_drive_kernel<MODEL, true>), grid, block, 0, st, tr->view, A);
+  else hipLaunchKernelGGL((pid_drive_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
+}
+
 extern "C" {
 
 int mr_version(void) { return MR_ABI_VERSION; }
@@ -1087,6 +1119,40 @@ int mr_plant_rollout(int32_t model, int32_t T, const double* log, int32_t n_star
   (void)hipFree(A.partials);
   HIP_TRY(el);
   HIP_TRY(es);
+  return MR_OK;
+}
+
+int mr_pid_gains_default(double* gains) {
+  if (!gains) return fail(MR_ERR_ARG, "null argument");
+  pid_gains_default(gains);
+  return MR_OK;
+}
+
+int mr_pid_control(const mr_track* tr, int32_t n, const double* state, double* mem, int32_t G, const double* gains,
+                   double dt, double* out, void* hip_stream) {
+  if (!tr) return fail(MR_ERR_ARG, "null track");
+  if (const char* e = pid_control_check(n, G, dt)) return fail(MR_ERR_ARG, e);
+  if (!state || !mem || !gains || !out) return fail(MR_ERR_ARG, "null argument");
+  MR_TRACK_LAUNCH(pid_control_kernel, state, mem, (int)G, gains, dt, out);
+}
+
+int mr_pid_drive(const mr_track* tr, int32_t model, int32_t n, int32_t T, double dt, double* state, double* mem,
+                 int32_t G, const double* gains, int32_t P, const double* params, uint32_t log_mask, double* log,
+                 int32_t* ticks_done, void* hip_stream) {
+  if (!tr) return fail(MR_ERR_ARG, "null track");
+  if (const char* e = pid_drive_check(model, n, T, dt, G, P, log_mask, log)) return fail(MR_ERR_ARG, e);
+  if (!state || !mem || !gains || !params || !ticks_done) return fail(MR_ERR_ARG, "null argument");
+  if (n == 0) return MR_OK;
+  MR_GUARD_DEVICE(tr->device);
+  PidDriveArgs A;
+  A.n = n; A.T = T; A.G = G; A.P = P; A.dt = dt;
+  A.state = state; A.mem = mem; A.gains = gains; A.params = params;
+  A.log_mask = log_mask; A.log = log; A.ticks_done = ticks_done;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (model == MR_PLANT_KINEMATIC) pid_drive_launch<PLANT_KIN>(tr, A, st);
+  else if (model == MR_PLANT_DYNAMIC) pid_drive_launch<PLANT_DYN>(tr, A, st);
+  else pid_drive_launch<PLANT_BLEND>(tr, A, st);
+  HIP_TRY(hipGetLastError());
   return MR_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "mr_tyrefit.h"
 #include "mr_rollout.h"
 #include "mr_plantroll.h"
+#include "mr_pid.h"
 
 using namespace mr;
 
@@ -454,6 +455,39 @@ int mrh_pacejka_dparams(const double* a, double Fz, double alpha, double* Fy, do
   double d[4];
   *Fy = pacejka_partials(t.c, alpha, d);
   pacejka_chain(t, a, Fz, d, dFy_da);
+  return 0;
+}
+
+// ---- the PID agent (mr_pid.h): the blob arguments of mrh_agent_sense ----
+int mrh_pid_gains_default(double* gains) {
+  pid_gains_default(gains);
+  return 0;
+}
+int mrh_pid_control(const double* blob, int nt, double L, int n_rows, int n, const double* state, double* mem, int G,
+                    const double* gains, double dt, double* out) {
+  if (const char* e = pid_control_check(n, G, dt)) return tyrefit_fail(e);
+  if (!blob || !state || !mem || !gains || !out) return tyrefit_fail("null argument");
+  TrackView T = track_view(blob, nt, L, n_rows);
+  for (int i = 0; i < n; ++i) pid_control_vehicle(T, n, i, state, mem, G, gains, dt, out);
+  return 0;
+}
+int mrh_pid_drive(const double* blob, int nt, double L, int n_rows, int model, int n, int T, double dt, double* state,
+                  double* mem, int G, const double* gains, int P, const double* params, uint32_t log_mask,
+                  double* log, int32_t* ticks_done, int nthreads) {
+  if (const char* e = pid_drive_check(model, n, T, dt, G, P, log_mask, log)) return tyrefit_fail(e);
+  if (!blob || !state || !mem || !gains || !params || !ticks_done) return tyrefit_fail("null argument");
+  const TrackView Tr = track_view(blob, nt, L, n_rows);
+  PidDriveArgs A;
+  A.n = n; A.T = T; A.G = G; A.P = P; A.dt = dt;
+  A.state = state; A.mem = mem; A.gains = gains; A.params = params;
+  A.log_mask = log_mask; A.log = log; A.ticks_done = ticks_done;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int i = 0; i < n; ++i) {
+    const double* q = params + (int64_t)(P == 1 ? 0 : i) * MR_PLANT_NPAR;
+    if (model == PLANT_KIN) pid_drive_vehicle<PLANT_KIN>(Tr, A, i, true, q, PidVoteLane());
+    else if (model == PLANT_DYN) pid_drive_vehicle<PLANT_DYN>(Tr, A, i, true, q, PidVoteLane());
+    else pid_drive_vehicle<PLANT_BLEND>(Tr, A, i, true, q, PidVoteLane());
+  }
   return 0;
 }
 

@@ -9,3 +9,5 @@ and synthetic workloads (``track``, ``workload``).  The drop-in modules that
 mirror the reference layout live beside it: ``control/``, ``models/``.
 """
 __version__ = "0.1.0"
+
+from . import pid  # noqa: E402,F401  (the PID agent: pid.gains, pid.control, pid.drive, pid.evaluate_gains)

@@ -13,6 +13,7 @@ MR_PREC = {"fp64": 0, "fp32": 1}
 MR_TYRE = {"linear": 0, "pacejka": 1}
 MR_PLANT = {"kin": 0, "dyn": 1, "blend": 2}
 MR_PLANT_NPAR = 22  # include/mpcracing.h
+MR_PID_NGAIN, MR_PID_NMEM, MR_PID_NOUT, MR_PID_NLOG = 8, 4, 8, 14  # include/mpcracing.h
 MR_OPT = {"sgd": 0, "adam": 1, "adamw": 2}
 STATUS = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "failed", 4: "infeasible"}
 
@@ -59,7 +60,8 @@ EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_
            "mr_track_polyfit", "mr_track_polyfit_deg", "mr_track_lookup_error", "mr_track_projection", "mr_track_prep",
            "mr_spline_from_waypoints", "mr_track_lane_table", "mr_agent_sense", "mr_plant_step",
            "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout",
-           "mr_plant_params_default", "mr_plant_step_params", "mr_plant_rollout"]
+           "mr_plant_params_default", "mr_plant_step_params", "mr_plant_rollout",
+           "mr_pid_gains_default", "mr_pid_control", "mr_pid_drive"]
 
 
 def _bind_product(lib):
@@ -98,6 +100,9 @@ def _bind_product(lib):
     lib.mr_plant_params_default.argtypes = [_PD]
     lib.mr_plant_step_params.argtypes = [_I32, _I32, V, V, _D, _I32, V, V, V]
     lib.mr_plant_rollout.argtypes = [_I32, _I32, V, _I32, V, _I32, _I32, V, V, V, V, V, V]
+    lib.mr_pid_gains_default.argtypes = [_PD]
+    lib.mr_pid_control.argtypes = [V, _I32, V, V, _I32, V, _D, V, V]
+    lib.mr_pid_drive.argtypes = [V, _I32, _I32, _I32, _D, V, V, _I32, V, _I32, V, ctypes.c_uint32, V, V, V]
     return lib
 
 
@@ -153,5 +158,8 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_plant_params_default.argtypes = [_PD]
     lib.mrh_plant_step_params.argtypes = [I, I, V, V, _D, I, V, V]
     lib.mrh_plant_rollout.argtypes = [I, I, V, I, V, I, I, V, V, V, V, V, I]
+    lib.mrh_pid_gains_default.argtypes = [_PD]
+    lib.mrh_pid_control.argtypes = [V, I, _D, I, I, V, V, I, V, _D, V]
+    lib.mrh_pid_drive.argtypes = [V, I, _D, I, I, I, I, _D, V, V, I, V, I, V, ctypes.c_uint32, V, V, I]
     lib.mrh_pacejka_dparams.argtypes = [_PD, _D, _D, _PD, _PD]
     return lib

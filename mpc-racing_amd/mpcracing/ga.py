@@ -30,6 +30,11 @@ def compute_avg_time(segment_time, average_time):
 def segment_times(records, s_start, s_end, length, dt):
     """First crossing time of s_end [B] by the progress records (track wrap handled)."""
     prog = np.stack([r["progress"].cpu().numpy() for r in records])          # [T][B]
+    return crossing_times(prog, s_start, s_end, length, dt)
+
+
+def crossing_times(prog, s_start, s_end, length, dt):
+    """``segment_times`` on the progress array [T][B] itself."""
     travelled = np.mod(prog - s_start[None, :], length)                      # distance along the lap
     # the first ticks may sit slightly behind the start (projection): treat > L/2 as negative
     travelled = np.where(travelled > 0.5 * length, travelled - length, travelled)

@@ -38,6 +38,19 @@ def _val(x):
     return None if math.isnan(x) else x
 
 
+def steps_line(r, i, dt, mpc_time=0):
+    """One row of ``steps.csv`` for vehicle ``i`` of the tick record ``r`` (NaN -> ``None``; the CARLA
+    lane-boundary points are ``None``)."""
+    row = dict(steps=int(r["step"]), X=_val(_host(r["X"], i)), Y=_val(_host(r["Y"], i)),
+               yaw=_val(_host(r["yaw"], i)), vx=_val(_host(r["vx"], i)), vy=_val(_host(r["vy"], i)),
+               yawdot=_val(_host(r["yawdot"], i)), progress=_val(_host(r["progress"], i)),
+               error=_val(_host(r["error"], i)), cmd_throttle=_val(_host(r["cmd_throttle"], i)),
+               cmd_steer=_val(_host(r["cmd_steer"], i)), cmd_brake=_val(_host(r["cmd_brake"], i)),
+               next_left_lane_point_x=None, next_left_lane_point_y=None, next_right_lane_point_x=None,
+               next_right_lane_point_y=None, last_ts=dt, mpc_time=mpc_time)
+    return ",".join(str(row[k]) for k in MEMBER_NAMES) + "\n"
+
+
 def write_run(records, run_dir, vehicle=0, dt=0.05, mpc_times=None):
     """records: ``mpcracing.ClosedLoop.run`` output; one vehicle's run into ``run_dir``."""
     from models.State import State
@@ -51,14 +64,7 @@ def write_run(records, run_dir, vehicle=0, dt=0.05, mpc_times=None):
             step = int(r["step"])
             mean_ts = mean_ts + ((dt - mean_ts) / (step + 1))
             mpc_time = 0 if mpc_times is None else mpc_times[step]
-            row = dict(steps=step, X=_val(_host(r["X"], i)), Y=_val(_host(r["Y"], i)),
-                       yaw=_val(_host(r["yaw"], i)), vx=_val(_host(r["vx"], i)), vy=_val(_host(r["vy"], i)),
-                       yawdot=_val(_host(r["yawdot"], i)), progress=_val(_host(r["progress"], i)),
-                       error=_val(_host(r["error"], i)), cmd_throttle=_val(_host(r["cmd_throttle"], i)),
-                       cmd_steer=_val(_host(r["cmd_steer"], i)), cmd_brake=_val(_host(r["cmd_brake"], i)),
-                       next_left_lane_point_x=None, next_left_lane_point_y=None, next_right_lane_point_x=None,
-                       next_right_lane_point_y=None, last_ts=dt, mpc_time=mpc_time)
-            f.write(",".join(str(row[k]) for k in MEMBER_NAMES) + "\n")
+            f.write(steps_line(r, i, dt, mpc_time))
             if r["controlled"]:
                 X = _host(r["predicted_states"], i)   # [6][N+1]
                 U = _host(r["controls"], i)           # [2][N]
