@@ -37,7 +37,7 @@ extern "C" {
    mr_outputs.lam_g / timeline, mr_config without lane_penalty (hard lane rows), status 4 = infeasible;
    102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
    mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout,
-   mr_pid_gains_default, mr_pid_control, mr_pid_drive) */
+   mr_pid_gains_default, mr_pid_control, mr_pid_drive, mr_pid_segment_times, mr_ga_random, mr_ga_breed) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -395,6 +395,52 @@ int mr_pid_control(const mr_track* tr, int32_t n, const double* state, double* m
 int mr_pid_drive(const mr_track* tr, int32_t model, int32_t n, int32_t T, double dt, double* state, double* mem,
                  int32_t G, const double* gains, int32_t P, const double* params, uint32_t log_mask, double* log,
                  int32_t* ticks_done, void* hip_stream);
+/* The fitness of the gain-tuning GA (GA/pdGA.py:48-55) in one launch without a log: vehicle i of n (a multiple
+   of K) drives segment i % K with gains row i / K of gains [n / K][8], from start [6][K] with s_start [K] as its
+   first previous progress, against plant `model` with params [P][MR_PLANT_NPAR] (P == 1 or n); start, s_start
+   and s_end [K] are read-only.  Every tick takes from the sensed progress what the host loop over the progress
+   row took: travelled = mod(progress - s_start, L), minus L above L / 2; at the first tick k with travelled >=
+   mod(s_end - s_start, L) =: need, times[i] = dt ((k - 1) + (need - a) / (c - a)), a and c the previous and the
+   current travelled; inf when k is 0, when the vehicle stops first (mr_pid_drive's rule) or when T ticks do not
+   reach it.  A vehicle with its time drives no further, and a wavefront ends when all its vehicles have:
+   ticks_done [n] is the number of ticks driven, the crossing tick included.  1 <= T <= 4096. */
+int mr_pid_segment_times(const mr_track* tr, int32_t model, int32_t n, int32_t K, int32_t T, double dt,
+                         const double* start, const double* s_start, const double* s_end, const double* gains,
+                         int32_t P, const double* params, double* times, int32_t* ticks_done, void* hip_stream);
+
+/* ---- the GA's step on the device (csrc/mr_ga.h) -----------------------------------------------------------
+ * GA/pdGA.py:57-91 with the rewards of GA/mpcGA.py:40-56.  The random stream is counter-based: draw j of
+ * (seed, island, generation) is numpy.random.Philox(key=[seed, island], counter=[0, 0, generation,
+ * 0]).random_raw()[j] (Philox4x64-10), its double (raw >> 11) * 2^-53 as numpy's Generator.random(); a draw
+ * depends on nothing else. */
+/* out[j] = raw draw first + j, j < count (HOST pointer; needs no GPU). */
+int mr_ga_random(uint64_t seed, uint64_t island, uint64_t generation, uint64_t first, int64_t count, uint64_t* out);
+/* One generation of n_island islands, one wavefront each (DEVICE pointers on the device that owns `genes`).
+   Gene d of individual i of island j is genes[(j P + i) ld + col[d]] (in/out): ld the row stride in doubles,
+   col the genes' distinct columns in [0, ld), NULL for 0 .. D-1 -- so the genes may be columns of wider rows,
+   such as the PID gains [.][8] that mr_pid_segment_times reads, and a packed population is ld = D, col = NULL.
+   times [n_island][P][K] (a non-finite time: segment not finished), avg
+   [n_island][K] in/out, 2 <= P <= 64, 1 <= K <= 64, 1 <= D <= 16, 1 <= pairs, 2 pairs <= P; lo, hi [D] or NULL,
+   a NaN entry for no bound.  In this order:
+   1. rewards (mpcGA.py:40-56), i ascending and k ascending within i: a = avg[k]; a finite t[i][k] sets
+      avg[k] = lambda_T t + (1 - lambda_T) a and adds exp(-kT (t - a)) to r[i]; an unfinished segment adds
+      nothing and leaves the average (an addition: the reference's average would turn inf);
+   2. roulette selection (pdGA.py:57-62): parent = the first j with u cdf[P-1] < cdf[j] (P - 1 if none), cdf the
+      cumulative sum of r in index order; floor(u P) when cdf[P-1] is 0 or not finite; parents are read from the
+      population as it was on entry;
+   3. pair m takes draws m (3 + 4 D) + ...: parent a, parent b, crossover point 1 + floor(u (D - 1)), then the D
+      mutation flags and the D mutation values of child 0 = a[:pt] ++ b[pt:], then those of child 1 = b[:pt] ++
+      a[pt:] (:64-69); where flag < mutation_rate, gene += value - 0.5 (:71-76); then the clip to lo, hi;
+   4. the 2 pairs lowest rewards in ascending order, ties to the lower index (NaN last), take child 0 and
+      child 1 of pairs 0, 1, ... (:87);
+   5. r [n_island][P]; best_r, best_idx [n_island] and best_genes [n_island][D]: the first maximum of r and
+      its genes as they were on entry (:89-91).
+   The island of the stream is island0 + the island's index in the call.  The reference's constants are kT = 4,
+   lambda_T = 0.3, mutation_rate = 0.4 (pdGA.py:9-13). */
+int mr_ga_breed(int32_t n_island, int32_t P, int32_t K, int32_t D, int32_t pairs, double* genes, int32_t ld,
+                const int32_t* col /* HOST, [D] or NULL */, const double* times, double* avg, const double* lo, const double* hi, double kT, double lambda_T, double mutation_rate,
+                uint64_t seed, uint64_t island0, uint64_t generation, double* r, double* best_r, int32_t* best_idx,
+                double* best_genes, void* hip_stream);
 
 #ifdef __cplusplus
 }

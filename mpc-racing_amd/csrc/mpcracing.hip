@@ -20,6 +20,7 @@
 #include "mr_rollout.h"
 #include "mr_plantroll.h"
 #include "mr_pid.h"
+#include "mr_ga.h"
 #include <vector>
 
 using namespace mr;
@@ -602,6 +603,35 @@ static void pid_drive_launch(const mr_track* tr, const PidDriveArgs& A, hipStrea
   else hipLaunchKernelGGL((pid_drive_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
 }
 
+// Segment times fused into the drive (mr_pid.h pid_segment_vehicle): the launch shape and the parameter staging
+// of pid_drive_kernel; the loop ends as soon as every lane of the wave has its time or has stopped.  Lanes are
+// dealt segment by segment (lane j of the launch drives gains row j % (n / K) on segment j / (n / K)): the
+// vehicles of a wave then share a segment, finish within a few ticks of each other, and the wave ends with them
+// instead of waiting for the slowest segment of the lap.  A vehicle's result does not depend on its lane.
+template <int MODEL, bool SHARED>
+__global__ __launch_bounds__(64) void pid_segment_kernel(TrackView T, PidSegArgs A) {
+  const int j = blockIdx.x * 64 + threadIdx.x, G = A.n / A.K;
+  const bool active = j < A.n;
+  const int i = active ? (j % G) * A.K + j / G : 0;
+  double q[MR_PLANT_NPAR];
+  const double* src = A.params + (SHARED ? (int64_t)0 : (int64_t)(active ? i : 0) * MR_PLANT_NPAR);
+  for (int j = 0; j < MR_PLANT_NPAR; ++j) q[j] = src[j];
+  pid_segment_vehicle<MODEL>(T, A, i, active, q, PidVoteWave());
+}
+template <int MODEL>
+static void pid_segment_launch(const mr_track* tr, const PidSegArgs& A, hipStream_t st) {
+  const dim3 grid((unsigned)((A.n + 63) / 64)), block(64);
+  if (A.P == 1) hipLaunchKernelGGL((pid_segment_kernel<MODEL, true>), grid, block, 0, st, tr->view, A);
+  else hipLaunchKernelGGL((pid_segment_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
+}
+
+// One generation of the GA (mr_ga.h): one wavefront per island, its exchange buffers in LDS.
+__global__ __launch_bounds__(64) void ga_breed_kernel(GaBreedArgs A) {
+  __shared__ GaShared sh;
+  Wv w{(int)threadIdx.x};
+  ga_breed_island(w, A, (int)blockIdx.x, &sh);
+}
+
 extern "C" {
 
 int mr_version(void) { return MR_ABI_VERSION; }
@@ -1152,6 +1182,59 @@ int mr_pid_drive(const mr_track* tr, int32_t model, int32_t n, int32_t T, double
   if (model == MR_PLANT_KINEMATIC) pid_drive_launch<PLANT_KIN>(tr, A, st);
   else if (model == MR_PLANT_DYNAMIC) pid_drive_launch<PLANT_DYN>(tr, A, st);
   else pid_drive_launch<PLANT_BLEND>(tr, A, st);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_pid_segment_times(const mr_track* tr, int32_t model, int32_t n, int32_t K, int32_t T, double dt,
+                         const double* start, const double* s_start, const double* s_end, const double* gains,
+                         int32_t P, const double* params, double* times, int32_t* ticks_done, void* hip_stream) {
+  if (!tr) return fail(MR_ERR_ARG, "null track");
+  if (const char* e = pid_segment_check(model, n, K, T, dt, P)) return fail(MR_ERR_ARG, e);
+  if (!start || !s_start || !s_end || !gains || !params || !times || !ticks_done)
+    return fail(MR_ERR_ARG, "null argument");
+  if (n == 0) return MR_OK;
+  MR_GUARD_DEVICE(tr->device);
+  PidSegArgs A;
+  A.n = n; A.T = T; A.K = K; A.P = P; A.dt = dt;
+  A.start = start; A.s_start = s_start; A.s_end = s_end; A.gains = gains; A.params = params;
+  A.times = times; A.ticks_done = ticks_done;
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (model == MR_PLANT_KINEMATIC) pid_segment_launch<PLANT_KIN>(tr, A, st);
+  else if (model == MR_PLANT_DYNAMIC) pid_segment_launch<PLANT_DYN>(tr, A, st);
+  else pid_segment_launch<PLANT_BLEND>(tr, A, st);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_ga_random(uint64_t seed, uint64_t island, uint64_t generation, uint64_t first, int64_t count, uint64_t* out) {
+  if (count < 0) return fail(MR_ERR_ARG, "count < 0");
+  if (count > 0 && !out) return fail(MR_ERR_ARG, "null argument");
+  GaStream rs(seed, island, generation);
+  for (int64_t j = 0; j < count; ++j) out[j] = rs.raw(first + (uint64_t)j);
+  return MR_OK;
+}
+
+int mr_ga_breed(int32_t n_island, int32_t P, int32_t K, int32_t D, int32_t pairs, double* genes, int32_t ld, const int32_t* col,
+                const double* times,
+                double* avg, const double* lo, const double* hi, double kT, double lambda_T, double mutation_rate,
+                uint64_t seed, uint64_t island0, uint64_t generation, double* r, double* best_r, int32_t* best_idx,
+                double* best_genes, void* hip_stream) {
+  if (const char* e = ga_breed_check(n_island, P, K, D, pairs, ld, col, kT, lambda_T, mutation_rate)) return fail(MR_ERR_ARG, e);
+  if (!genes || !times || !avg || !r || !best_r || !best_idx || !best_genes) return fail(MR_ERR_ARG, "null argument");
+  if (n_island == 0) return MR_OK;
+  int dev = -1;
+  if (pointer_device(genes, &dev) != 0) return fail(MR_ERR_ARG, "genes is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  GaBreedArgs A;
+  A.n_island = n_island; A.P = P; A.K = K; A.D = D; A.pairs = pairs;
+  A.kT = kT; A.lambda_T = lambda_T; A.mutation_rate = mutation_rate;
+  A.seed = seed; A.island0 = island0; A.generation = generation;
+  A.ld = ld;
+  for (int d = 0; d < MR_GA_D_MAX; ++d) A.col[d] = col && d < D ? col[d] : d;
+  A.genes = genes; A.times = times; A.avg = avg; A.lo = lo; A.hi = hi;
+  A.r = r; A.best_r = best_r; A.best_idx = best_idx; A.best_genes = best_genes;
+  hipLaunchKernelGGL(ga_breed_kernel, dim3((unsigned)n_island), dim3(64), 0, (hipStream_t)hip_stream, A);
   HIP_TRY(hipGetLastError());
   return MR_OK;
 }

@@ -16,6 +16,7 @@
 #include "mr_rollout.h"
 #include "mr_plantroll.h"
 #include "mr_pid.h"
+#include "mr_ga.h"
 
 using namespace mr;
 
@@ -487,6 +488,71 @@ int mrh_pid_drive(const double* blob, int nt, double L, int n_rows, int model, i
     if (model == PLANT_KIN) pid_drive_vehicle<PLANT_KIN>(Tr, A, i, true, q, PidVoteLane());
     else if (model == PLANT_DYN) pid_drive_vehicle<PLANT_DYN>(Tr, A, i, true, q, PidVoteLane());
     else pid_drive_vehicle<PLANT_BLEND>(Tr, A, i, true, q, PidVoteLane());
+  }
+  return 0;
+}
+
+// ---- the GA (mr_ga.h, mr_pid.h pid_segment_vehicle): one lane at a time for the drive, an emulated wave per island ----
+int mrh_pid_segment_times(const double* blob, int nt, double L, int n_rows, int model, int n, int K, int T, double dt,
+                          const double* start, const double* s_start, const double* s_end, const double* gains, int P,
+                          const double* params, double* times, int32_t* ticks_done, int nthreads) {
+  if (const char* e = pid_segment_check(model, n, K, T, dt, P)) return tyrefit_fail(e);
+  if (!blob || !start || !s_start || !s_end || !gains || !params || !times || !ticks_done)
+    return tyrefit_fail("null argument");
+  const TrackView Tr = track_view(blob, nt, L, n_rows);
+  PidSegArgs A;
+  A.n = n; A.T = T; A.K = K; A.P = P; A.dt = dt;
+  A.start = start; A.s_start = s_start; A.s_end = s_end; A.gains = gains; A.params = params;
+  A.times = times; A.ticks_done = ticks_done;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int i = 0; i < n; ++i) {
+    const double* q = params + (int64_t)(P == 1 ? 0 : i) * MR_PLANT_NPAR;
+    if (model == PLANT_KIN) pid_segment_vehicle<PLANT_KIN>(Tr, A, i, true, q, PidVoteLane());
+    else if (model == PLANT_DYN) pid_segment_vehicle<PLANT_DYN>(Tr, A, i, true, q, PidVoteLane());
+    else pid_segment_vehicle<PLANT_BLEND>(Tr, A, i, true, q, PidVoteLane());
+  }
+  return 0;
+}
+int mrh_ga_random(uint64_t seed, uint64_t island, uint64_t generation, uint64_t first, int64_t count, uint64_t* out) {
+  if (count < 0) return tyrefit_fail("count < 0");
+  if (count > 0 && !out) return tyrefit_fail("null argument");
+  GaStream rs(seed, island, generation);
+  for (int64_t j = 0; j < count; ++j) out[j] = rs.raw(first + (uint64_t)j);
+  return 0;
+}
+struct BreedJob {
+  const GaBreedArgs* A;
+  int island;
+  GaShared* sh;
+};
+static void breed_body(HostWave* hw, int lane, void* arg) {
+  BreedJob* j = (BreedJob*)arg;
+  Wv w{lane, hw};
+  ga_breed_island(w, *j->A, j->island, j->sh);
+  wsync(w);
+}
+int mrh_ga_breed(int n_island, int P, int K, int D, int pairs, double* genes, int ld, const int32_t* col,
+                 const double* times, double* avg,
+                 const double* lo, const double* hi, double kT, double lambda_T, double mutation_rate, uint64_t seed,
+                 uint64_t island0, uint64_t generation, double* r, double* best_r, int32_t* best_idx,
+                 double* best_genes) {
+  if (const char* e = ga_breed_check(n_island, P, K, D, pairs, ld, col, kT, lambda_T, mutation_rate)) return tyrefit_fail(e);
+  if (!genes || !times || !avg || !r || !best_r || !best_idx || !best_genes) return tyrefit_fail("null argument");
+  GaBreedArgs A;
+  A.n_island = n_island; A.P = P; A.K = K; A.D = D; A.pairs = pairs;
+  A.kT = kT; A.lambda_T = lambda_T; A.mutation_rate = mutation_rate;
+  A.seed = seed; A.island0 = island0; A.generation = generation;
+  A.ld = ld;
+  for (int d = 0; d < MR_GA_D_MAX; ++d) A.col[d] = col && d < D ? col[d] : d;
+  A.genes = genes; A.times = times; A.avg = avg; A.lo = lo; A.hi = hi;
+  A.r = r; A.best_r = best_r; A.best_idx = best_idx; A.best_genes = best_genes;
+  for (int i = 0; i < n_island; ++i) {
+    GaShared* sh = new GaShared();
+    BreedJob job{&A, i, sh};
+    HostWave* hw = new HostWave();
+    host_wave_run(*hw, &breed_body, &job);
+    delete hw;
+    delete sh;
   }
   return 0;
 }

@@ -183,4 +183,76 @@ MR_HD void pid_drive_vehicle(const TrackView& Tr, const PidDriveArgs& A, int i, 
   A.ticks_done[i] = done;
 }
 
+// ---- segment times fused into the drive: the fitness of the gain-tuning GA (GA/pdGA.py:48-55) ----
+struct PidSegArgs {
+  int n, T, K, P;
+  double dt;
+  const double* start;    // [6][K] start state of every segment (read-only: every generation reuses it)
+  const double* s_start;  // [K] the first previous progress
+  const double* s_end;    // [K]
+  const double* gains;    // [n / K][8]
+  const double* params;   // [P][MR_PLANT_NPAR]
+  double* times;          // [n]
+  int32_t* ticks_done;    // [n]
+};
+
+inline const char* pid_segment_check(int64_t model, int64_t n, int64_t K, int64_t T, double dt, int64_t P) {
+  if (model < PLANT_KIN || model > PLANT_BLEND) return "unknown plant model";
+  if (n < 0) return "n < 0";
+  if (n > (int64_t)0x7fffffff / MR_PID_NLOG) return "too many vehicles";
+  if (K < 1) return "K < 1";
+  if (n % K != 0) return "n must be a multiple of K (vehicle i drives segment i % K with gains row i / K)";
+  if (T < 1) return "T < 1";
+  if (T > MR_PID_T_MAX) return "T > 4096";
+  if (!plant_dt_ok(dt)) return "dt must be a positive finite number";
+  if (P != 1 && P != n) return "P must be 1 (shared parameters) or n (one vector per vehicle)";
+  return nullptr;
+}
+
+// The drive of pid_drive_vehicle without a log: vehicle i starts segment i % K with gains row i / K, and every
+// tick takes from its sensed progress what ga.crossing_times takes from the progress row: travelled =
+// py_mod(progress - s_start, L), minus L above L / 2; at the first tick k with travelled >= need =
+// py_mod(s_end - s_start, L) the time is dt ((k - 1) + (need - a) / (c - a)), a and c the previous and the
+// current travelled; inf when k is 0; a NaN progress never hits.  A vehicle that has its time or has stopped (the
+// drive's rule) is finished; the loop ends when every lane of the wave is.  ticks_done: the ticks driven, the
+// crossing tick included.
+template <int MODEL, class Vote>
+MR_HD void pid_segment_vehicle(const TrackView& Tr, const PidSegArgs& A, int i, bool active, const double* q,
+                               const Vote& any_alive) {
+  const int iv = active ? i : 0;  // idle lanes of the last wave follow vehicle 0 and never store
+  const int K = A.K, seg = iv % K;
+  const double* gp = A.gains + (int64_t)(iv / K) * MR_PID_NGAIN;
+  double x[6], m[MR_PID_NMEM], g[MR_PID_NGAIN];
+  for (int c = 0; c < 6; ++c) x[c] = A.start[(int64_t)c * K + seg];
+  const double s_start = A.s_start[seg];
+  m[0] = s_start; m[1] = 0; m[2] = 0; m[3] = NAN;
+  for (int c = 0; c < MR_PID_NGAIN; ++c) g[c] = gp[c];
+  const double L = Tr.L, need = py_mod(A.s_end[seg] - s_start, L);
+  bool alive = active;
+  int done = 0;
+  double tm = INFINITY, prev = 0;
+  for (int t = 0; t < A.T; ++t) {
+    if (!any_alive(alive)) break;
+    double mn[MR_PID_NMEM], o[MR_PID_NOUT], xn[6];
+    for (int c = 0; c < MR_PID_NMEM; ++c) mn[c] = m[c];
+    pid_control(Tr, x, mn, g, A.dt, o);
+    plant_step<MODEL>(q, x, o[2] - o[4], o[3], A.dt, xn);
+    bool ok = tf_finite(o[2]) && tf_finite(o[3]) && tf_finite(o[4]);
+    for (int c = 0; c < 6; ++c) ok = ok && tf_finite(x[c]) && tf_finite(xn[c]);
+    alive = alive && ok;
+    double tr = py_mod(o[0] - s_start, L);
+    tr = tr > 0.5 * L ? tr - L : tr;
+    const bool hit = alive && tr >= need;
+    if (hit && t > 0) tm = A.dt * ((double)(t - 1) + (need - prev) / (tr - prev));
+    prev = tr;
+    for (int c = 0; c < 6; ++c) x[c] = alive ? xn[c] : x[c];
+    for (int c = 0; c < MR_PID_NMEM; ++c) m[c] = alive ? mn[c] : m[c];
+    done += alive ? 1 : 0;
+    alive = alive && !hit;
+  }
+  if (!active) return;
+  A.times[i] = tm;
+  A.ticks_done[i] = done;
+}
+
 }  // namespace mr

@@ -7,7 +7,10 @@ brake floor of 0.5.  ``control`` is one ``Agent.run_step`` for a batch of vehicl
 csrc/mr_pid.h: one lane per vehicle, state, memory and gains in registers, one launch per 4096 ticks) and
 returns the drive as logs that ``rollout.load_log`` / ``rollout_errors`` / ``plantfit`` take;
 ``evaluate_gains`` is the fitness of the gain-tuning GA (GA/pdGA.py:48-55): segment times of a population of
-gain vectors, every (individual, segment) pair one vehicle of one drive.
+gain vectors, every (individual, segment) pair one vehicle of one drive.  ``segment_times`` gives the same times
+without the log, taken as the vehicles drive (``mr_pid_segment_times``: a vehicle's drive ends at its crossing), and
+``tune_gains`` is the GA itself: per generation that launch and one ``mr_ga_breed`` (csrc/mr_ga.h, ``ga.breed``),
+all generations on one stream with one synchronise.
 
 ``host_twin=True`` runs the g++ build of the same source instead (TEST-ONLY, explicit; there is no fallback:
 without it a missing GPU or library is an error).
@@ -254,3 +257,136 @@ def evaluate_gains(track, population, bounds, ticks, v0=15.0, model="blend", par
                 rows=["progress"], host_twin=host_twin, device=device)
     t = crossing_times(res.rows["progress"], s0, np.tile(ends, P), tr.length, dt)
     return t.reshape(P, K), res
+
+
+def _full_gains(population):
+    """[G][8]: gain vectors given whole, or as the GA's four (kP_steer, kD_steer, kP_throttle, kD_throttle) in
+    the default gains"""
+    pop = np.atleast_2d(np.asarray(population, np.float64))
+    if pop.shape[1] == 4:
+        full = np.tile(gains(), (pop.shape[0], 1))
+        full[:, 2:6] = pop
+        pop = full
+    elif pop.shape[1] != abi.MR_PID_NGAIN:
+        raise ValueError(f"gains: expected [G][4] or [G][{abi.MR_PID_NGAIN}], got {pop.shape}")
+    return np.ascontiguousarray(pop)
+
+
+class _SegmentDrive:
+    """The read-only side of ``mr_pid_segment_times`` on a backend: the segments' start states, bounds and the
+    plant parameters, put there once; ``launch`` only enqueues."""
+
+    def __init__(self, track, bounds, n_gain, v0, model, params, dt, host_twin, device):
+        from .closed_loop import ClosedLoop
+        self.tr = _track(track, host_twin, device)
+        self.host_twin = host_twin
+        bounds = np.asarray(bounds, np.float64)
+        if bounds.ndim != 1 or len(bounds) < 2:
+            raise ValueError("bounds: expected [K + 1] with K >= 1")
+        self.K = len(bounds) - 1
+        self.n = int(n_gain) * self.K
+        self.model_id, q = rollout._plant_args(model, params)
+        if q.shape[0] not in (1, self.n):
+            raise ValueError(f"params: expected one vector or n = {self.n}, got {q.shape[0]}")
+        self.P, self.dt = q.shape[0], float(dt)
+        self.be = be = _backend(self.tr, host_twin)
+        x0 = ClosedLoop.start_states(self.tr, bounds[:-1], v0=v0)
+        self.start, self.s_start, self.s_end, self.q = be.put(x0), be.put(bounds[:-1]), be.put(bounds[1:]), be.put(q)
+
+    def launch(self, d_gains, ticks, d_times, d_done):
+        be = self.be
+        p = lambda a: None if a is None else be.ptr(a)  # noqa: E731
+        args = [self.model_id, self.n, self.K, int(ticks), self.dt, p(self.start), p(self.s_start), p(self.s_end),
+                p(d_gains), self.P, p(self.q), p(d_times), p(d_done)]
+        if self.host_twin:
+            be.check(be.lib.mrh_pid_segment_times(*self.tr.args(), *args, 16))
+        else:
+            be.check(be.lib.mr_pid_segment_times(self.tr.h, *args, be.stream()))
+
+    def sync(self):
+        if not self.host_twin:
+            self.be.torch.cuda.synchronize(self.be.dev)
+
+
+def segment_times(track, gains, bounds, ticks, v0=15.0, model="blend", params=None, dt=0.05, host_twin=False,
+                  device=0):
+    """The times of ``evaluate_gains`` (bit for bit) without its log: G gain vectors ([G][4] or [G][8], as there)
+    on K segments (bounds [K+1]) in one ``mr_pid_segment_times`` launch that takes each vehicle's crossing time
+    from its progress as it drives and ends a vehicle's drive there (csrc/mr_pid.h pid_segment_vehicle).
+    1 <= ticks <= 4096.  Returns (times [G][K], inf where the segment's end is not reached; ticks_done [G][K],
+    the ticks driven, the crossing tick included)."""
+    g = _full_gains(gains)
+    sd = _SegmentDrive(track, bounds, g.shape[0], v0, model, params, dt, host_twin, device)
+    be = sd.be
+    d_g, t, done = be.put(g), be.empty((sd.n,)), be.empty((sd.n,), np.int32)
+    sd.launch(d_g, ticks, t, done)
+    sd.sync()
+    return np.array(be.get(t)).reshape(-1, sd.K), np.array(be.get(done)).reshape(-1, sd.K)
+
+
+class TuneResult:
+    """A GA run of ``tune_gains``: ``population`` [I][P][D] (the final genes) and ``gains`` [I][P][8] (the gain
+    vectors they make); per generation and island ``best_reward`` [G][I], ``best_index`` [G][I] and ``best_genes``
+    [G][I][D] (the best individual of the generation as it was scored); ``avg`` [I][K] the final running averages;
+    ``rewards`` [I][P] and ``ticks_done`` [I][P][K] of the last generation; ``times`` [G][I][P][K] with
+    ``keep_times`` (else None); ``genes`` the gene names."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def tune_gains(track, bounds, generations, islands=1, population=10, pairs=1, seed=0,
+               genes=("kP_steer", "kD_steer", "kP_throttle", "kD_throttle"), init=None, lo=None, hi=None, avg0=None,
+               keep_times=False, ticks=240, v0=15.0, model="blend", params=None, dt=0.05, kT=4.0, lambda_T=0.3,
+               mutation_rate=0.4, host_twin=False, device=0):
+    """The reference's gain-tuning GA (GA/pdGA.py) with the fitness it never had: ``islands`` independent
+    populations of ``population`` gain vectors over ``generations`` generations, every (individual, segment) pair
+    one vehicle.  Everything stays on the device: per generation one ``mr_pid_segment_times`` launch (the segment
+    times of all islands) and one ``mr_ga_breed`` launch (rewards, selection, crossover, mutation and replacement,
+    one wavefront per island, on the gain rows themselves), 2 * generations launches on one stream and one
+    synchronise at the end.
+
+    genes: the tuned ``GAIN_FIELDS`` (the others keep their defaults); init [I][P][D] (or [P][D] for every
+    island), default uniform [0, 1) from the stream (seed, island, generation 2**32 - 1) (pdGA.py:23); lo, hi: gene
+    bounds (scalars or [D]); avg0: the segments' initial average times, a scalar, [K] or [I][K], default
+    ticks * dt / 2 (the reference's lap_time / num_checkpoints of TrackSegments can be passed here).  Generation g
+    draws from the stream (seed, island, g).  Returns a TuneResult."""
+    from . import ga
+    I, P, G = int(islands), int(population), int(generations)
+    if G < 1 or I < 1:
+        raise ValueError("generations and islands must be at least 1")
+    names = list(genes)
+    unknown = [k for k in names if k not in GAIN_FIELDS]
+    if unknown or len(set(names)) != len(names):
+        raise ValueError(f"genes: distinct names of {GAIN_FIELDS} expected, got {names}")
+    D = len(names)
+    cols = [GAIN_FIELDS.index(k) for k in names]
+    if init is None:
+        pop = np.stack([ga.random(seed, i, ga.INIT_GENERATION, 0, P * D, host_twin=host_twin).reshape(P, D)
+                        for i in range(I)])
+    else:
+        pop = np.array(np.broadcast_to(np.asarray(init, np.float64), (I, P, D)))
+    full = np.tile(gains(), (I * P, 1))
+    full[:, cols] = pop.reshape(I * P, D)
+    sd = _SegmentDrive(track, bounds, I * P, v0, model, params, dt, host_twin, device)
+    K, be = sd.K, sd.be
+    avg = np.array(np.broadcast_to(np.asarray(ticks * dt / 2 if avg0 is None else avg0, np.float64), (I, K)))
+    b = ga._bounds(lo, hi, D)
+    d_g, d_avg = be.put(full), be.put(avg)
+    d_b = be.put(b) if b is not None else None
+    d_t = be.empty((G if keep_times else 1, I * P * K))
+    d_done, d_r = be.empty((I * P * K,), np.int32), be.empty((I, P))
+    d_br, d_bi, d_bg = be.empty((G, I)), be.empty((G, I), np.int32), be.empty((G, I, D))
+    col = (ctypes.c_int32 * D)(*cols)
+    for g in range(G):
+        t = d_t[g if keep_times else 0]
+        sd.launch(d_g, ticks, t, d_done)
+        ga.breed_launch(be, host_twin, (I, P, K, D, int(pairs)), d_g, abi.MR_PID_NGAIN, col, t, d_avg, d_b,
+                        (kT, lambda_T, mutation_rate), seed, 0, g, d_r, d_br[g], d_bi[g], d_bg[g])
+    sd.sync()
+    out = np.array(be.get(d_g)).reshape(I, P, abi.MR_PID_NGAIN)
+    return TuneResult(population=out[:, :, cols].copy(), gains=out, best_reward=np.array(be.get(d_br)),
+                      best_index=np.array(be.get(d_bi)), best_genes=np.array(be.get(d_bg)),
+                      avg=np.array(be.get(d_avg)), rewards=np.array(be.get(d_r)),
+                      ticks_done=np.array(be.get(d_done)).reshape(I, P, K),
+                      times=np.array(be.get(d_t)).reshape(G, I, P, K) if keep_times else None, genes=names)
