@@ -1,0 +1,253 @@
+"""Generate tests/golden/ipopt_trace_golden.npz / .json: the dense IPOPT oracle's iteration log per case.
+
+TEST FIXTURE GENERATOR (CPU only; the GPU box never runs the oracle's solves).
+
+For each case oracle.ipopt.solve_ipopt(..., log=True, rules=PRODUCT) runs in fp64 on oracle.nlp.MPCProblem built
+as tests/test_ipopt_trajectory.py builds it, and the fixture keeps
+  <case>/log     [iterations][7]: kkt, mu, alpha, delta, theta, phi, in_resto of every logged iteration
+  <case>/lam_g   whole-solve cases: MPCProblem.lam_g_ipopt(r.nu, r.lam), the reference's opti.lam_g rows
+  <case>/in_*    the instance's inputs (B = 1, ABI layout), to check that mpcracing.workload still makes them
+  <case>/marker, <case>/fp32_dev   fp32 cases only, see below
+and, in the json index, the case's config / instance / options, the oracle's status, iters and obj, ``n_cmp``
+(the number of leading rows the tests compare) and the worst deviation of either host build on those rows.
+
+``n_cmp`` is set here, not by the tests: both host builds of the solver source (tests/host_twin.py, scalar=True
+and the emulated wavefront) solve the same instance, and n_cmp is the longest prefix of non-restoration rows on
+which both stay within N_CMP_RTOL = 1e-8 relative of the oracle in alpha, theta (plus 1e-10 absolute: near
+feasibility theta is roundoff of the defects) and kkt -- 100 times under the 1e-6 the tests apply, so a row that
+is compared is one on which the two linear algebras (dense LDL there, Riccati here) have not yet been separated
+by rounding.  mu and delta must be within 1e-12 on those rows.  Asserted, not measured (MIN_N_CMP): n_cmp is the
+whole solve for C2_1, C2_8, C4_0 and C5_0, at least 14 for the prefix cases and at least 30 for both C1dyn cases.
+A case whose solve converged and is compared to its last iteration is marked ``whole`` in the index; the tests
+then also compare its iteration count, status and objective.
+
+Cases
+  prefix, 14 iterations (tol 1e-8, acceptable 1e-6 over 15):  C2_5 and C2_6 (kinematic), C3_374 and C3_0
+      (dynamic, hard lane rows; 374 drives the inertia shift past 1e2), C4_7 (blended), C5_3 (blended, learned
+      Pacejka tyres).  Rows of the restoration phase end the prefix: the product does not restate restoration
+      iterates (none occurs in these 14).  C2_5 converges in 9 iterations at these options, so it cannot give 14
+      rows: it is kept, compared over its whole solve, and its neighbour C2_6 -- which converges in exactly 14 --
+      is added for the 14-row condition.
+  whole solve (tol 1e-10, acceptable_iter 0, lam_g):  C2_1, C2_8, C2_10, C4_0, C5_0 (delta reaches 100), C1dyn
+      (config 1 with the dynamic model; a backtracked step) and C1dyn_nan: C1dyn with state0's throttle / steer
+      absent (NaN) and the u_init of tests/test_duals.py::test_lam_g_state0_controls_none.  C2_10 misses the
+      whole-solve condition: at row 24 of its 27 the KKT error (8.7e-8) is a stationarity residual that is
+      cancellation of O(1e2) terms, and both host builds sit 3e-7 relative from the oracle there, above 1e-8.
+      Its place as a whole solve is taken by C2_8 (19 iterations; the nearer neighbours 9 and 11 qualify as
+      well but end in 12 - 13 iterations like C2_1); C2_10 stays with its first 24 rows and its lam_g.  The same
+      rounding ends C1dyn at row 52 of 66 and C1dyn_nan at row 30 of 31.
+  fp32 (the reference's options: tol 1e-4, acceptable 1e-2 over 15; first 8 rows):  C4_0_ref, C5_0_ref.  With
+      the oracle's rows the fixture keeps ``marker``, the trace markers (line-search trial counts, watchdog /
+      correction codes) of the host fp64 wave build on those rows -- the oracle's log carries no marker column;
+      the fp64 build is asserted to sit within 1e-8 of the oracle on every one of these rows, so its markers are
+      those of the oracle's trajectory -- and ``fp32_dev``, the host wave *fp32* build's worst relative deviation
+      from the oracle's rows per column of FP32_COLS (its markers are asserted equal to ``marker``).
+
+Usage: python tests/golden/make_ipopt_trace_golden.py        (about 1 minute, 8 worker processes)
+"""
+import json
+import os
+import sys
+import time
+
+for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
+    os.environ.setdefault(_v, "1")  # one thread per worker process: the dense solves are small
+
+import numpy as np  # noqa: E402
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.abspath(os.path.join(HERE, "..", ".."))
+sys.path.insert(0, os.path.join(REPO, "mpc-racing_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.insert(0, REPO)
+
+NPZ = os.path.join(HERE, "ipopt_trace_golden.npz")
+INDEX = os.path.join(HERE, "ipopt_trace_golden.json")
+
+K_PREFIX = 14
+K_FP32 = 8
+# the options of the oracle and of every build compared with it (max_iter ends a prefix case after its rows)
+PREFIX_OPT = dict(tol=1e-8, acceptable_tol=1e-6, acceptable_iter=15, max_iter=K_PREFIX)
+WHOLE_OPT = dict(tol=1e-10, acceptable_tol=1e-6, acceptable_iter=0, max_iter=500)
+REF_OPT = dict(tol=1e-4, acceptable_tol=1e-2, acceptable_iter=15, max_iter=K_FP32)  # control/MPC.py:152-161
+N_CMP_RTOL = 1e-8
+THETA_ATOL = 1e-10
+TRACE_CAP = 520  # host builds; the longest solve here takes 86 iterations
+
+# case -> (config, instance, kind)
+CASES = {
+    "C2_5": ("C2", 5, "prefix"),
+    "C2_6": ("C2", 6, "prefix"),
+    "C3_374": ("C3", 374, "prefix"),
+    "C3_0": ("C3", 0, "prefix"),
+    "C4_7": ("C4", 7, "prefix"),
+    "C5_3": ("C5", 3, "prefix"),
+    "C2_1": ("C2", 1, "whole"),
+    "C2_8": ("C2", 8, "whole"),
+    "C2_10": ("C2", 10, "whole"),
+    "C4_0": ("C4", 0, "whole"),
+    "C5_0": ("C5", 0, "whole"),
+    "C1dyn": ("C1", 0, "whole"),
+    "C1dyn_nan": ("C1", 0, "whole"),
+    "C4_0_ref": ("C4", 0, "fp32"),
+    "C5_0_ref": ("C5", 0, "fp32"),
+}
+# the least n_cmp a case must reach; None: the whole solve, to its last iteration
+MIN_N_CMP = {"prefix": K_PREFIX, "fp32": K_FP32, "whole": None, "C1dyn": 30, "C1dyn_nan": 30, "C2_5": None,
+             "C2_10": K_PREFIX}
+OPTIONS = {"prefix": PREFIX_OPT, "whole": WHOLE_OPT, "fp32": REF_OPT}
+
+# trace columns of include/mpcracing.h (mr_outputs.trace) and where the oracle's log keeps the same quantity
+TRACE_COL = dict(kkt=0, mu=1, alpha=2, alpha_dual=3, delta=4, theta=5, phi=6, marker=7)
+LOG_COL = dict(kkt=0, mu=1, alpha=2, delta=3, theta=4, phi=5, in_resto=6)
+FP32_COLS = ("kkt", "mu", "alpha", "delta", "theta", "phi")
+IN_KEYS = ("state0", "s0", "cx", "cy", "max_error", "runtime", "u_init")
+
+
+def case_config(case):
+    """The solver's configuration of the case: mpcracing.workload.CONFIGS, C1dyn with the dynamic model."""
+    from mpcracing import workload as wl
+    cfg = dict(wl.CONFIGS[CASES[case][0]])
+    if case.startswith("C1dyn"):
+        cfg["model"] = "dyn"
+    return cfg
+
+
+def case_tyres(case):
+    from mpcracing import workload as wl
+    t = case_config(case)["tyres"]
+    return wl.tyre_coeffs(t) if t else None
+
+
+def case_inputs(case):
+    """The case's instance as a batch of one (ABI layout), made by mpcracing.workload."""
+    from mpcracing import workload as wl
+    name, i, _kind = CASES[case]
+    b = wl.make_batch(name, limit=i + 1)
+    sub = {k: (np.ascontiguousarray(v[..., i:i + 1]) if v is not None else None) for k, v in b.items()}
+    if case == "C1dyn_nan":  # tests/test_duals.py::test_lam_g_state0_controls_none
+        sub["state0"][6:, 0] = np.nan
+        rng = np.random.default_rng(3)
+        u = np.stack([rng.uniform(-0.5, 0.8, 20), rng.uniform(-0.3, 0.3, 20)])
+        u[:, -1] = u[:, -2]  # a shifted last_controls repeats its last column (MPC.py:120-121)
+        sub["u_init"] = u[:, :, None].copy()
+    return sub
+
+
+def rel_dev(mine, ref, atol=0.0):
+    """Per-row deviation of ``mine`` from ``ref`` relative to |ref| after an absolute allowance; a row whose
+    reference is 0 deviates by 0 if it is matched exactly and by inf otherwise."""
+    mine, ref = np.asarray(mine, np.float64), np.asarray(ref, np.float64)
+    d = np.maximum(np.abs(mine - ref) - atol, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(d == 0.0, 0.0, d / np.abs(ref))
+
+
+def _oracle(case):
+    import torch
+    torch.set_num_threads(1)
+    from mpcracing import workload as wl
+    from oracle.ipopt import PRODUCT, solve_ipopt
+    from oracle.nlp import MPCProblem
+    _name, _i, kind = CASES[case]
+    cfg, sub = case_config(case), case_inputs(case)
+    inst = wl.instance_dicts(sub)[0]
+    kw = {}
+    if sub["u_init"] is not None:  # MPCProblem shifts last_controls itself: lc[1:] + [lc[-1]] == the columns
+        cols = [(float(a), float(s)) for a, s in zip(*sub["u_init"][:, :, 0])]
+        kw["last_controls"] = [(0.0, 0.0)] + cols[:-1]
+    p = MPCProblem(inst["state0"], inst["s0"], inst["cx"], inst["cy"], inst["max_error"], N=cfg["N"], Ts=cfg["Ts"],
+                   model=cfg["model"], lane_bounds=cfg["lane"], tyres=case_tyres(case), **kw)
+    o = OPTIONS[kind]
+    t0 = time.time()
+    r = solve_ipopt(p, tol=o["tol"], max_iter=o["max_iter"], acceptable_tol=o["acceptable_tol"],
+                    acceptable_iter=o["acceptable_iter"], log=True, rules=PRODUCT)
+    log = np.array([[kkt, mu, alpha, delta, th, ph, float(resto)]
+                    for (_k, kkt, mu, alpha, delta, th, ph, resto) in r.log]).reshape(-1, 7)
+    res = dict(log=log, status=int(r.status), iters=int(r.iters), obj=float(r.obj), seconds=time.time() - t0)
+    if kind == "whole":
+        assert r.status == 0, (case, r.status)
+        res["lam_g"] = p.lam_g_ipopt(r.nu, r.lam)
+    return res
+
+
+def host_trace(case, scalar, precision="fp64"):
+    """The case's solve by a host build of the solver source (every output of tests/host_twin.solve)."""
+    import host_twin as ht
+    cfg = case_config(case)
+    c = ht.config(cfg["N"], cfg["model"], precision, cfg["lane"], cfg["Ts"], **OPTIONS[CASES[case][2]])
+    return ht.solve(c, case_inputs(case), tyres=case_tyres(case), nthreads=1, scalar=scalar, trace_instance=0,
+                    trace_cap=TRACE_CAP, duals=not scalar)
+
+
+def _n_cmp(case, log):
+    """(n_cmp, worst deviations over those rows) from both host fp64 builds."""
+    n = len(log)
+    ok = log[:, LOG_COL["in_resto"]] == 0.0
+    worst = {}
+    devs = {}
+    for scalar in (True, False):
+        tr = host_trace(case, scalar)["trace"][:n]
+        ok &= tr[:, TRACE_COL["marker"]] > -200.0  # the product's own restoration rows
+        for col in ("alpha", "theta", "kkt", "mu", "delta"):
+            d = rel_dev(tr[:, TRACE_COL[col]], log[:, LOG_COL[col]], THETA_ATOL if col == "theta" else 0.0)
+            devs[col, scalar] = d
+            if col in ("alpha", "theta", "kkt"):
+                ok &= d <= N_CMP_RTOL
+    bad = np.nonzero(~ok)[0]
+    n_cmp = int(bad[0]) if bad.size else n
+    for (col, scalar), d in devs.items():
+        worst[col] = max(worst.get(col, 0.0), float(d[:n_cmp].max(initial=0.0)))
+    assert worst["mu"] <= 1e-12 and worst["delta"] <= 1e-12, (case, worst)
+    return n_cmp, worst
+
+
+def main():
+    from multiprocessing import Pool
+    with Pool(8) as pool:
+        res = dict(zip(CASES, pool.map(_oracle, list(CASES), chunksize=1)))
+    assemble(res)
+
+
+def assemble(res):
+    """Set n_cmp from the host builds, assert the cases' conditions and write the fixture."""
+    arrays, index = {}, {}
+    for case, (name, i, kind) in CASES.items():
+        r = res[case]
+        log = r["log"]
+        n_cmp, worst = _n_cmp(case, log)
+        need = MIN_N_CMP.get(case, MIN_N_CMP[kind])
+        whole = r["status"] == 0 and n_cmp == len(log) == r["iters"]  # compared to its last iteration
+        assert whole if need is None else n_cmp >= need, (case, n_cmp, len(log), r["status"], need)
+        arrays[f"{case}/log"] = log
+        for k, v in case_inputs(case).items():
+            if v is not None:
+                arrays[f"{case}/in_{k}"] = v
+        if "lam_g" in r:
+            arrays[f"{case}/lam_g"] = r["lam_g"]
+        entry = dict(config=name, instance=i, kind=kind, options=OPTIONS[kind], status=r["status"],
+                     iters=r["iters"], obj=r["obj"], rows=len(log), n_cmp=n_cmp, whole=whole,
+                     max_delta=float(log[:, LOG_COL["delta"]].max()), host_worst_dev=worst)
+        if kind == "fp32":
+            assert n_cmp == K_FP32 == len(log), (case, n_cmp, len(log))
+            m64 = host_trace(case, False)["trace"][:K_FP32, TRACE_COL["marker"]]
+            t32 = host_trace(case, False, "fp32")["trace"][:K_FP32]
+            assert np.array_equal(t32[:, TRACE_COL["marker"]], m64), (case, t32[:, TRACE_COL["marker"]], m64)
+            dev = np.array([rel_dev(t32[:, TRACE_COL[c]], log[:, LOG_COL[c]]).max() for c in FP32_COLS])
+            assert np.isfinite(dev).all(), (case, dev)  # delta's zero rows are zero in fp32 too
+            arrays[f"{case}/marker"] = m64
+            arrays[f"{case}/fp32_dev"] = dev
+            entry["host_fp32_dev"] = dict(zip(FP32_COLS, dev.tolist()))
+        index[case] = entry
+        print(case, f"oracle {r['seconds']:.1f} s", json.dumps(entry), flush=True)
+    np.savez_compressed(NPZ, **arrays)
+    with open(INDEX, "w") as f:
+        json.dump(index, f, indent=1, sort_keys=True)
+        f.write("\n")
+    size = os.path.getsize(NPZ) + os.path.getsize(INDEX)
+    assert size < 100 * 1024, size
+    print("wrote", NPZ, INDEX, size, "bytes")
+
+
+if __name__ == "__main__":
+    main()

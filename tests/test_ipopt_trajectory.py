@@ -16,6 +16,13 @@ watchdog / SOC / least-squares multipliers) -- none of which is reached in these
 Tolerances: alpha, theta 1e-6 relative (different linear algebra, same arithmetic; theta also 1e-10
 absolute: near feasibility it is roundoff of the defects), delta and mu exact to 1e-12 (they are products
 of IPOPT's constants).
+
+Below the two live-oracle tests, the same comparison runs against the oracle's committed log
+(tests/golden/ipopt_trace_golden.npz, generator make_ipopt_trace_golden.py; bars in tests/ipopt_trace_cases.py)
+for both host builds -- the scalar solver and the emulated wavefront, the kernel's own source -- over the
+kinematic, dynamic + lane rows, blended and blended + Pacejka models: five 14-iteration prefixes and six whole
+solves at tol 1e-10 (iterations, status, objective, and for the wave build lam_g -- the scalar build exports
+none).  tests/test_gpu_ipopt_trajectory.py holds the gfx950 build to the same fixture.
 """
 import os
 import sys
@@ -30,6 +37,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(REPO, "mpc-racing_amd"))
 
 import host_twin as ht  # noqa: E402
+import ipopt_trace_cases as itc  # noqa: E402
 from mpcracing import workload as wl  # noqa: E402
 
 
@@ -84,3 +92,73 @@ def test_whole_solve_matches_dense_ipopt(i):
         np.testing.assert_allclose(o["trace"][j, 0], row[1], rtol=1e-6, err_msg=f"iteration {j}: kkt")
         np.testing.assert_allclose(o["trace"][j, 1], row[2], rtol=1e-12, err_msg=f"iteration {j}: mu")
     np.testing.assert_allclose(o["obj"][0], r.obj, rtol=1e-10)
+
+
+# ---- the oracle's committed log (tests/golden/ipopt_trace_golden.npz) against both host builds ----
+
+_solves = {}
+
+
+def _host(case, scalar):
+    """One host solve per (case, build), shared by the tests below."""
+    if (case, scalar) not in _solves:
+        _solves[case, scalar] = itc.GEN.host_trace(case, scalar)
+    return _solves[case, scalar]
+
+
+def test_ipopt_trace_fixture():
+    """The fixture itself: its inputs are what mpcracing.workload makes today, every case keeps its promised
+    number of comparable rows, and the inertia correction is exercised (delta > 1e2 in C3_374, >= 100 in C5_0:
+    without those the shift's growth rule would go unchecked)."""
+    arrays, index = itc.fixture()
+    G = itc.GEN
+    assert sorted(index) == sorted(G.CASES)
+    assert os.path.getsize(G.NPZ) + os.path.getsize(G.INDEX) < 100 * 1024
+    for case, (name, i, kind) in G.CASES.items():
+        e = index[case]
+        assert (e["config"], e["instance"], e["kind"], e["options"]) == (name, i, kind, G.OPTIONS[kind])
+        sub = G.case_inputs(case)
+        for k in G.IN_KEYS:
+            if sub[k] is None:
+                assert f"{case}/in_{k}" not in arrays, (case, k)
+            else:
+                assert np.array_equal(arrays[f"{case}/in_{k}"], sub[k], equal_nan=True), (case, k)
+        log = arrays[f"{case}/log"]
+        assert log.shape == (e["rows"], 7) and np.isfinite(log).all()
+        need = G.MIN_N_CMP.get(case, G.MIN_N_CMP[kind])
+        assert e["whole"] == (e["status"] == 0 and e["n_cmp"] == e["rows"] == e["iters"])
+        assert e["whole"] if need is None else need <= e["n_cmp"] <= e["rows"]
+        assert not log[:e["n_cmp"], itc.LOG_COL["in_resto"]].any()
+        assert max(e["host_worst_dev"][c] for c in ("alpha", "theta", "kkt")) <= G.N_CMP_RTOL
+        if kind == "whole":
+            assert e["status"] == 0 and arrays[f"{case}/lam_g"].shape == (13 * G.case_config(case)["N"] + 9 -
+                                                                          2 * (case == "C1dyn_nan"),)
+        if kind == "fp32":
+            assert arrays[f"{case}/marker"].shape == (G.K_FP32,)
+            assert arrays[f"{case}/fp32_dev"].shape == (len(G.FP32_COLS),)
+    d = itc.LOG_COL["delta"]
+    assert arrays["C3_374/log"][:index["C3_374"]["n_cmp"], d].max() > 1e2
+    assert arrays["C5_0/log"][:, d].max() >= 100.0
+    assert np.isnan(arrays["C1dyn_nan/in_state0"][6:]).all()
+
+
+@pytest.mark.parametrize("scalar", [True, False], ids=["scalar", "wave"])
+@pytest.mark.parametrize("case", itc.cases("prefix", "whole"))
+def test_host_build_iterates_match_oracle_log(case, scalar):
+    """alpha, theta, kkt to 1e-6, mu and delta to 1e-12 over the case's n_cmp rows; a whole solve that is compared
+    to its end also stops at the oracle's iteration with its status and (to 1e-10) its objective."""
+    label = "scalar" if scalar else "wave"
+    o = _host(case, scalar)
+    itc.check_rows(case, o["trace"], label)
+    itc.check_whole(case, o["status"][0], o["iters"][0], o["obj"][0], label)
+
+
+@pytest.mark.parametrize("case", itc.cases("whole"))
+def test_wave_lam_g_matches_oracle_log(case):
+    """The emulated wave's exported lam_g against the oracle's multipliers in Opti row order; C1dyn_nan: the two
+    state0 rows absent (NaN), the other 13N+7 matching."""
+    o = _host(case, False)
+    assert o["status"][0] == 0
+    lam = o["lam_g"][:, 0]
+    assert np.isnan(lam[-2:]).all() == (case == "C1dyn_nan") and not np.isnan(lam[:-2]).any()
+    itc.check_lam_g(case, lam, "wave")
