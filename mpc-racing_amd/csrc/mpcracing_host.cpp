@@ -17,6 +17,7 @@
 #include "mr_plantroll.h"
 #include "mr_pid.h"
 #include "mr_ga.h"
+#include "mr_probe.h"
 
 using namespace mr;
 
@@ -553,6 +554,115 @@ int mrh_ga_breed(int n_island, int P, int K, int D, int pairs, double* genes, in
     host_wave_run(*hw, &breed_body, &job);
     delete hw;
     delete sh;
+  }
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- probes of the wave primitives and the fp32 pieces (mr_probe.h): the bodies that
+// libmpcracing_probe.so runs on gfx950, here under the fibre emulation / with libm ----
+template <typename T>
+struct PrimsJob {
+  int wg, n_wg;
+  T* in;
+  T* out;
+};
+template <typename T>
+static void prims_wave_body(HostWave* hw, int lane, void* arg) {
+  PrimsJob<T>* j = (PrimsJob<T>*)arg;
+  Wv w{lane, hw};
+  probe::prims_body<T>(w, j->wg, j->n_wg, j->in, j->out);
+  wsync(w);
+}
+template <typename T>
+static int run_prims_host(int n_wg, T* in, T* out) {
+  if (n_wg < 1 || !in || !out) return -1;
+  for (int g = 0; g < n_wg; ++g) {
+    PrimsJob<T> job{g, n_wg, in, out};
+    HostWave* hw = new HostWave();
+    host_wave_run(*hw, &prims_wave_body<T>, &job);
+    delete hw;
+  }
+  return 0;
+}
+template <typename T>
+struct MfmaJob {
+  int wg;
+  const T *A, *B, *C;
+  T* D;
+};
+template <typename T>
+static void mfma_wave_body(HostWave* hw, int lane, void* arg) {
+  MfmaJob<T>* j = (MfmaJob<T>*)arg;
+  Wv w{lane, hw};
+  probe::mfma_body<T>(w, j->wg, j->A, j->B, j->C, j->D);
+  wsync(w);
+}
+template <typename T>
+static int run_mfma_host(int n_wg, const T* A, const T* B, const T* C, T* D) {
+  if (n_wg < 1 || !A || !B || !C || !D) return -1;
+  for (int g = 0; g < n_wg; ++g) {
+    MfmaJob<T> job{g, A, B, C, D};
+    HostWave* hw = new HostWave();
+    host_wave_run(*hw, &mfma_wave_body<T>, &job);
+    delete hw;
+  }
+  return 0;
+}
+
+extern "C" {
+
+void mrh_probe_layout(int32_t* out8) {
+  out8[0] = probe::PRIMS_IN_W; out8[1] = probe::PRIMS_OUT_W; out8[2] = probe::MFMA_A_W; out8[3] = probe::MFMA_B_W;
+  out8[4] = probe::MFMA_C_W; out8[5] = probe::MFMA_D_W; out8[6] = probe::PS_COUNT; out8[7] = 0;
+}
+int mrh_wave_prims_f32(int n_wg, float* in, float* out) { return run_prims_host<float>(n_wg, in, out); }
+int mrh_wave_prims_f64(int n_wg, double* in, double* out) { return run_prims_host<double>(n_wg, in, out); }
+int mrh_wave_prims_i32(int n_wg, int32_t* in, int32_t* out) { return run_prims_host<int>(n_wg, in, out); }
+int mrh_wave_mfma_f32(int n_wg, const float* A, const float* B, const float* C, float* D) {
+  return run_mfma_host<float>(n_wg, A, B, C, D);
+}
+int mrh_wave_mfma_f64(int n_wg, const double* A, const double* B, const double* C, double* D) {
+  return run_mfma_host<double>(n_wg, A, B, C, D);
+}
+
+// Dyn<float, MODEL> with libm (the host's fp32 build of the model), n points; J == NULL: value only
+int mrh_eval_dynamics_f32(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
+                          double Fz_back, int n, const float* x, const float* u, const float* nu, float* f, float* J,
+                          float* H) {
+  if (!c || n < 0 || !x || !u || !f || ((J != nullptr) != (H != nullptr)) || (J && !nu)) return -1;
+  TyreCoef<double> tf{}, tr{};
+  if (a_front) tf = pacejka_coef(a_front, Fz_front);
+  if (a_back) tr = pacejka_coef(a_back, Fz_back);
+  ProbParams<float> P;
+  fill_params<float>(*c, tf, tr, P);
+#define MR_CASE(M)                                                                                            \
+  for (int i = 0; i < n; ++i) {                                                                               \
+    if (J) Dyn<float, M>::fjh(P, x + 6 * i, u + 2 * i, nu + 6 * i, f + 6 * i, J + 48 * i, H + 36 * i);          \
+    else Dyn<float, M>::f(P, x + 6 * i, u + 2 * i, f + 6 * i);                                                \
+  }
+  switch (c->model) {
+    case MR_MODEL_KINEMATIC: MR_CASE(MODEL_KIN) break;
+    case MR_MODEL_DYNAMIC: MR_CASE(MODEL_DYN) break;
+    case MR_MODEL_BLENDED: MR_CASE(MODEL_BLEND) break;
+    case MR_MODEL_BLENDED_PACEJKA: MR_CASE(MODEL_BLEND_PACEJKA) break;
+    case MR_MODEL_DYNAMIC_PACEJKA: MR_CASE(MODEL_DYN_PACEJKA) break;
+    default: return -1;
+  }
+#undef MR_CASE
+  return 0;
+}
+
+// chol3r + lsolve3r + ltsolve3r in float with libm, n systems (R packed r00 r10 r20 r11 r21 r22)
+int mrh_chol3_f32(int n, const float* R, const float* b, int32_t* ok, float* L, float* iv, float* x) {
+  if (n < 0 || !R || !b || !ok || !L || !iv || !x) return -1;
+  for (int i = 0; i < n; ++i) {
+    float xl[3] = {b[3 * i], b[3 * i + 1], b[3 * i + 2]};
+    ok[i] = chol3r(R + 6 * i, L + 6 * i, iv + 3 * i) ? 1 : 0;
+    lsolve3r(L + 6 * i, iv + 3 * i, xl);
+    ltsolve3r(L + 6 * i, iv + 3 * i, xl);
+    for (int j = 0; j < 3; ++j) x[3 * i + j] = xl[j];
   }
   return 0;
 }

@@ -32,8 +32,15 @@ MR_HD float mr_cos(float a) { return cosf(a); }
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(MR_LIBM_F32)
 // fp32 on the device, for the model's steering and slip angles (|a| < 1.6 rad): tan from the hardware
 // sine / cosine (the library tanf carries a ~140-instruction large-argument reduction), atan2 by an
-// odd degree-15 polynomial on [0, 1] with octant reduction (max error 1.3e-7 rad, ~2 ulp, vs ~45
-// instructions with a division for the library's).  fp64 and the host build keep libm.
+// odd degree-15 polynomial on [0, 1] with octant reduction (vs ~45 instructions with a division for the
+// library's).  The polynomial alone, evaluated exactly, is within 6.4e-8 rad of atan on [0, 1] (the 1.3e-7
+// once quoted here is about that plus one rounding of a result near pi / 4, 6.0e-8; it left out the reciprocal,
+// the octant subtractions and the small angles), but its leading coefficient 0.99999946 leaves a relative
+// error of 5.4e-7 (4.5 ulp) as the angle goes to 0 -- the range of the slip angles.  The whole function,
+// measured on an MI355X over the plane and the solver's range (tests/test_gpu_f32_math.py,
+// profiles/f32_accuracy.json): 2.8e-7 rad absolute (near +-3 pi / 4), 6.8e-7 relative for |angle| < 0.1;
+// the test holds it to 5.5e-7 and 9.0e-7.  Zeros: (+-0, x >= 0) gives +-0, (+-0, x < 0) +-pi, (y, +-0)
+// +-pi / 2 as atan2f; (+0, -0) gives 0 where atan2f gives pi.  fp64 and the host build keep libm.
 MR_HD float mr_tan(float a) { return __sinf(a) * __builtin_amdgcn_rcpf(__cosf(a)); }
 MR_HD float mr_atan2(float y, float x) {
   const float ax = fabsf(x), ay = fabsf(y);
@@ -124,6 +131,49 @@ template <typename T> MR_HD Jet2<T> japply(Jet2<T> a, T f0, T f1, T f2) {
   return {f0, f1 * a.d, f2 * a.d * a.d + f1 * a.dd};
 }
 
+// fp32 forms of the two quotients of the tyre law for arguments past the 1e-3 series switch of pacejka_jet.  The
+// direct forms there cancel: (q x - atan x) / x^2 and (z cos z - sin z) / z^2 lose ~ eps / x^2, hundreds of eps32
+// in the law's second derivative for |B alpha| in 1e-3 .. 0.1 (tests/test_gpu_f32_dynamics.py).  Below 0.25 (0.5
+// for the sine quotient) a series with constant coefficients, truncated below eps32 / 2 of its leading term;
+// above, the direct form, whose cancellation is then <= 24 eps32 of a term that is itself small against 1.
+// g(x) = atan(x) / x - 1 composed with the jet x:
+template <typename T>
+MR_HD Jet2<T> atanc_m1_jet(Jet2<T> x) {
+  if (mr_abs(x.v) < T(0.25)) {
+    // g = s (-1/3 + s/5 - s^2/7 + s^3/9 - s^4/11 + s^5/13), s = x^2; next term 3 x^12 / 15 of the leading one
+    Jet2<T> s = jmul(x, x);
+    Jet2<T> p = jaddc(jscale(s, T(1.0 / 13.0)), T(-1.0 / 11.0));
+    p = jaddc(jmul(s, p), T(1.0 / 9.0));
+    p = jaddc(jmul(s, p), T(-1.0 / 7.0));
+    p = jaddc(jmul(s, p), T(1.0 / 5.0));
+    p = jaddc(jmul(s, p), T(-1.0 / 3.0));
+    return jmul(s, p);
+  }
+  const T xv = x.v, at = mr_atan(xv), q = T(1) / (T(1) + xv * xv);
+  const T n = q * xv - at;  // x^2 g'
+  const T g0 = at / xv - T(1), g1 = n / (xv * xv);
+  const T g2 = (T(-2) * xv * q * q * xv * xv * xv - T(2) * xv * n) / (xv * xv * xv * xv);
+  return japply(x, g0, g1, g2);
+}
+// S(z) = sin(z) / z composed with the jet z:
+template <typename T>
+MR_HD Jet2<T> sinc_jet(Jet2<T> z) {
+  const T zv = z.v, s = zv * zv;
+  T s0, s1, s2;
+  if (mr_abs(zv) < T(0.5)) {
+    // coefficients (-1)^k / (2k+1)!, times 2k for S' / z, times 2k (2k-1) for S''
+    s0 = T(1) + s * (T(-1.0 / 6.0) + s * (T(1.0 / 120.0) + s * (T(-1.0 / 5040.0) + s * (T(1.0 / 362880.0) + s * T(-1.0 / 39916800.0)))));
+    s1 = zv * (T(-1.0 / 3.0) + s * (T(1.0 / 30.0) + s * (T(-1.0 / 840.0) + s * (T(1.0 / 45360.0) + s * T(-1.0 / 3991680.0)))));
+    s2 = T(-1.0 / 3.0) + s * (T(1.0 / 10.0) + s * (T(-1.0 / 168.0) + s * (T(1.0 / 6480.0) + s * T(-1.0 / 443520.0))));
+  } else {
+    const T sn = mr_sin(zv), cs = mr_cos(zv);
+    s0 = sn / zv;
+    s1 = (zv * cs - sn) / s;
+    s2 = (T(2) * sn - T(2) * zv * cs - s * sn) / (s * zv);
+  }
+  return japply(z, s0, s1, s2);
+}
+
 // Pacejka lateral force with derivatives (stable form; series near 0 where the
 // learned coefficients live: |B*alpha| ~ 1e-7, |E| ~ 1e10).
 template <typename T>
@@ -136,6 +186,8 @@ MR_HD TyreJet<T> pacejka_jet(const TyreCoef<T>& c, T alpha) {
     // E*(atan(x)/x - 1) = K2*a^2*(-1/3 + x^2/5 - x^4/7)
     Jet2<T> poly = jaddc(jmul(x2, jaddc(jscale(x2, T(-1.0 / 7.0)), T(1.0 / 5.0))), T(-1.0 / 3.0));
     eg = jscale(jmul(jmul(a, a), poly), c.K2);
+  } else if constexpr (sizeof(T) == 4) {
+    eg = jscale(atanc_m1_jet(x), c.E);
   } else {
     T xv = x.v;
     T at = mr_atan(xv);
@@ -154,6 +206,10 @@ MR_HD TyreJet<T> pacejka_jet(const TyreCoef<T>& c, T alpha) {
     T c2 = c.C * c.C;
     Jet2<T> y2 = jmul(y, y);
     h = jaddc(jmul(y2, jaddc(jscale(y2, T(1.0 / 5.0) + c2 / T(6) + c2 * c2 / T(120)), -(T(1.0 / 3.0) + c2 / T(6)))), T(1));
+  } else if constexpr (sizeof(T) == 4) {
+    // h(y) = S(C y A(y)) A(y), A(y) = atan(y) / y: the same function without the direct form's cancellation
+    Jet2<T> A = jaddc(atanc_m1_jet(y), T(1));
+    h = jmul(sinc_jet(jscale(jmul(y, A), c.C)), A);
   } else {
     // h(y) = sin(C atan y)/(C y)
     T yv = y.v;

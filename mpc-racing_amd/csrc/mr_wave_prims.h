@@ -207,7 +207,11 @@ __device__ __forceinline__ void wgather(const Wv& w, T v, T* out) {
 // as DPP half-row / row mirrors (the same partners' values once quads / octets agree), 16 and
 // 32 as the gfx950 v_permlane16_swap / v_permlane32_swap.  Every level computes
 // op(own, partner) on every lane, as the xor butterfly does; the host emulation below uses the
-// same partners in the same order, so sums round identically on both.
+// same partners in the same order, so sums round identically on both (tests/test_gpu_wave_prims.py compares
+// both with a restatement, bit for bit).  A NaN: wmax / wmin (b > a ? b : a) keep it only where it is a level's
+// own value, so with a NaN in one lane the result is NOT lane-uniform -- NaN on that lane alone, and on the other lanes
+// maxima that may miss the values the NaN displaced on its way up (2 - 3 distinct results over the wave;
+// measured on gfx950, identical in the emulation); callers reduce NaN-free values or test for the NaN with wany.
 __device__ __forceinline__ int dpp_bits(int v, int ctrl_sel) {
   switch (ctrl_sel) {
     case 0: return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]

@@ -6,6 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.abspath(os.path.join(HERE, "..", "csrc"))
 PRODUCT_LIB = os.path.join(CSRC, "libmpcracing.so")
 HOST_TWIN_LIB = os.path.join(CSRC, "libmpcracing_host.so")
+PROBE_LIB = os.path.join(CSRC, "libmpcracing_probe.so")  # TEST-ONLY (csrc/mr_probe.hip), not part of the C ABI
 
 ABI_VERSION = 103  # MR_ABI_VERSION of include/mpcracing.h
 MR_MODEL = {"kin": 0, "dyn": 1, "blend": 2, "blend_pacejka": 3, "dyn_pacejka": 4}
@@ -131,6 +132,36 @@ def load_product(path=None):
     return _product
 
 
+# operations of mrp_math_f32 (csrc/mr_probe.hip MathOp)
+MRP_OP = {"sin": 0, "cos": 1, "tan": 2, "atan": 3, "atan2": 4, "sqrt": 5, "exp": 6, "log": 7, "rsqrt": 8, "div": 9,
+          "rcp": 10}
+_probe = None
+
+
+def load_probe(path=None):
+    """TEST-ONLY gfx950 probes of the device-only fp32 functions and the wave primitives (csrc/mr_probe.hip,
+    the product's compiler flags).  Like the product: a missing library is an error, there is no fallback."""
+    global _probe
+    path = path or os.environ.get("MR_PROBE_LIB") or PROBE_LIB
+    if _probe is None:
+        if not os.path.exists(path):
+            raise RuntimeError(f"libmpcracing_probe.so not built ({path}); run `python __graft_entry__.py build`")
+        lib = ctypes.CDLL(path)
+        V, I = ctypes.c_void_p, _I32
+        lib.mrp_last_error.restype = ctypes.c_char_p
+        lib.mrp_layout.argtypes = [_PI32]
+        lib.mrp_layout.restype = None
+        lib.mrp_math_f32.argtypes = [I, I, V, V, V, V]
+        lib.mrp_eval_dynamics_f32.argtypes = [ctypes.POINTER(MRConfig), _PD, _D, _PD, _D, I, V, V, V, V, V, V, V]
+        lib.mrp_chol3_f32.argtypes = [I, V, V, V, V, V, V, V]
+        for t in ("f32", "f64", "i32"):
+            getattr(lib, "mrp_wave_prims_" + t).argtypes = [I, V, V, V]
+        for t in ("f32", "f64"):
+            getattr(lib, "mrp_wave_mfma_" + t).argtypes = [I, V, V, V, V, V]
+        _probe = lib
+    return _probe
+
+
 def load_host_twin(path=HOST_TWIN_LIB):
     """TEST-ONLY host build of the same solver source (never used by the product path)."""
     lib = ctypes.CDLL(path)
@@ -171,4 +202,12 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_ga_random.argtypes = [_U64, _U64, _U64, _U64, ctypes.c_int64, V]
     lib.mrh_ga_breed.argtypes = [I] * 5 + [V, I, _PI32] + [V] * 4 + [_D] * 3 + [_U64] * 3 + [V] * 4
     lib.mrh_pacejka_dparams.argtypes = [_PD, _D, _D, _PD, _PD]
+    lib.mrh_probe_layout.argtypes = [_PI32]
+    lib.mrh_probe_layout.restype = None
+    for t in ("f32", "f64", "i32"):
+        getattr(lib, "mrh_wave_prims_" + t).argtypes = [I, V, V]
+    for t in ("f32", "f64"):
+        getattr(lib, "mrh_wave_mfma_" + t).argtypes = [I, V, V, V, V]
+    lib.mrh_eval_dynamics_f32.argtypes = [ctypes.POINTER(MRConfig), _PD, _D, _PD, _D, I, V, V, V, V, V, V]
+    lib.mrh_chol3_f32.argtypes = [I, V, V, V, V, V, V]
     return lib
