@@ -520,11 +520,11 @@ __global__ __launch_bounds__(64) void tyre_fit_kernel(TfFitArgs A) {
 // Open-loop rollouts (mr_rollout.h).  One wavefront per (parameter set, chunk of 64 starts); block b of the
 // launch is set p0 + b / n_chunk (the partials buffer holds the sets of this launch only).
 // 1 wave per SIMD (254 VGPRs); a bound of 2 measured the same (9.58 against 9.63 ms).
-__global__ __launch_bounds__(64, 1) void tyre_rollout_kernel(RoArgs A, int p0) {
+__global__ __launch_bounds__(64, 1) void tyre_rollout_kernel(mr_tyrefit_config cfg, RoArgs A, int p0) {
   __shared__ double lds[RO_LDS_WORDS];
   Wv w{(int)threadIdx.x};
   const int pl = (int)(blockIdx.x / A.n_chunk), chunk = (int)(blockIdx.x % A.n_chunk);
-  ro_chunk_kind(A, p0 + pl, pl, chunk, lds, w);
+  ro_chunk_kind(cfg, A, p0 + pl, pl, chunk, lds, w);
 }
 // one thread per (set of this launch, step): the chunks' partials added in chunk order
 __global__ __launch_bounds__(64) void tyre_rollout_finish_kernel(int H, int n_chunk, const double* partials, int p0,
@@ -558,11 +558,11 @@ __global__ __launch_bounds__(256) void plant_dt_check_kernel(const double* dt, i
 // finishing kernel and the start check are tyre_rollout_finish_kernel and tyre_start_check_kernel.  The blended
 // model needs the whole register file of 1 wave per SIMD (256 VGPRs + 10 AGPRs, no scratch).
 template <int MODEL>
-__global__ __launch_bounds__(64, 1) void plant_rollout_kernel(PrArgs A, int p0) {
+__global__ __launch_bounds__(64, 1) void plant_rollout_kernel(RoArgs A, int p0) {
   __shared__ double lds[RO_LDS_WORDS];
   Wv w{(int)threadIdx.x};
   const int pl = (int)(blockIdx.x / A.n_chunk), chunk = (int)(blockIdx.x % A.n_chunk);
-  pr_chunk<MODEL>(A, p0 + pl, pl, chunk, lds, w);
+  ro_chunk(A, RoPlantModel<MODEL>(A, p0 + pl), p0 + pl, pl, chunk, lds, w);
 }
 __global__ __launch_bounds__(kTrackBlock) void plant_step_params_kernel(int model, int n, const double* state,
                                                                         const double* cmd, double dt, int P,
@@ -586,21 +586,19 @@ __global__ __launch_bounds__(kTrackBlock) void pid_control_kernel(TrackView T, i
 struct PidVoteWave {
   __device__ __forceinline__ bool operator()(bool alive) const { return __builtin_amdgcn_ballot_w64(alive) != 0; }
 };
+// the parameter staging of the drive kernels: vehicle i's vector (idle lanes: vehicle 0's) or the shared one
+template <bool SHARED>
+__device__ __forceinline__ void pid_stage_params(const double* params, int i, bool active, double* q) {
+  const double* src = params + (SHARED ? (int64_t)0 : (int64_t)(active ? i : 0) * MR_PLANT_NPAR);
+  for (int j = 0; j < MR_PLANT_NPAR; ++j) q[j] = src[j];
+}
 template <int MODEL, bool SHARED>
 __global__ __launch_bounds__(64) void pid_drive_kernel(TrackView T, PidDriveArgs A) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   const bool active = i < A.n;
   double q[MR_PLANT_NPAR];
-  const double* src = A.params + (SHARED ? (int64_t)0 : (int64_t)(active ? i : 0) * MR_PLANT_NPAR);
-  for (int j = 0; j < MR_PLANT_NPAR; ++j) q[j] = src[j];
+  pid_stage_params<SHARED>(A.params, i, active, q);
   pid_drive_vehicle<MODEL>(T, A, i, active, q, PidVoteWave());
-}
-
-template <int MODEL>
-static void pid_drive_launch(const mr_track* tr, const PidDriveArgs& A, hipStream_t st) {
-  const dim3 grid((unsigned)((A.n + 63) / 64)), block(64);
-  if (A.P == 1) hipLaunchKernelGGL((pid_drive_kernel<MODEL, true>), grid, block, 0, st, tr->view, A);
-  else hipLaunchKernelGGL((pid_drive_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
 }
 
 // Segment times fused into the drive (mr_pid.h pid_segment_vehicle): the launch shape and the parameter staging
@@ -614,15 +612,8 @@ __global__ __launch_bounds__(64) void pid_segment_kernel(TrackView T, PidSegArgs
   const bool active = j < A.n;
   const int i = active ? (j % G) * A.K + j / G : 0;
   double q[MR_PLANT_NPAR];
-  const double* src = A.params + (SHARED ? (int64_t)0 : (int64_t)(active ? i : 0) * MR_PLANT_NPAR);
-  for (int j = 0; j < MR_PLANT_NPAR; ++j) q[j] = src[j];
+  pid_stage_params<SHARED>(A.params, i, active, q);
   pid_segment_vehicle<MODEL>(T, A, i, active, q, PidVoteWave());
-}
-template <int MODEL>
-static void pid_segment_launch(const mr_track* tr, const PidSegArgs& A, hipStream_t st) {
-  const dim3 grid((unsigned)((A.n + 63) / 64)), block(64);
-  if (A.P == 1) hipLaunchKernelGGL((pid_segment_kernel<MODEL, true>), grid, block, 0, st, tr->view, A);
-  else hipLaunchKernelGGL((pid_segment_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
 }
 
 // One generation of the GA (mr_ga.h): one wavefront per island, its exchange buffers in LDS.
@@ -630,6 +621,57 @@ __global__ __launch_bounds__(64) void ga_breed_kernel(GaBreedArgs A) {
   __shared__ GaShared sh;
   Wv w{(int)threadIdx.x};
   ga_breed_island(w, A, (int)blockIdx.x, &sh);
+}
+
+// A device-side argument check (mr_tyre_fit, mr_tyre_rollout, mr_plant_rollout): n flags zeroed on the device,
+// launch(flags) enqueues the checking kernels, the flags come back in bad[0..n).  Nothing the kernels test is
+// used as an index before it is known to be in range; the flags are freed on every path.
+template <class Launch>
+static int device_check(hipStream_t st, int n, int* bad, Launch&& launch) {
+  int* bad_dev = nullptr;
+  HIP_TRY(hipMalloc(&bad_dev, n * sizeof(int)));
+  hipError_t e0 = hipMemsetAsync(bad_dev, 0, n * sizeof(int), st);
+  launch(bad_dev);
+  hipError_t e1 = hipGetLastError();
+  hipError_t e2 = hipMemcpyAsync(bad, bad_dev, n * sizeof(int), hipMemcpyDeviceToHost, st);
+  hipError_t e3 = hipStreamSynchronize(st);
+  (void)hipFree(bad_dev);
+  HIP_TRY(e0);
+  HIP_TRY(e1);
+  HIP_TRY(e2);
+  HIP_TRY(e3);
+  return MR_OK;
+}
+static void start_check_launch(hipStream_t st, const RoArgs& A, int* flag) {
+  const int blocks = (A.n_start + 255) / 256;
+  hipLaunchKernelGGL(tyre_start_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, A.start,
+                     A.n_start, A.T - 1 - A.H, flag);
+}
+
+// The launches of every rollout: the partials of at most P_launch sets at a time (256 MiB; launches on one stream
+// reuse the buffer in order), per slice launch(A, grid, p0) -- the model's rollout kernel for sets p0 .. -- and the
+// finish kernel, then a synchronise, because the partials buffer is released here, on every path.
+template <class Launch>
+static int rollout_launch(hipStream_t st, RoArgs A, int P, double* stats, int32_t* count, Launch&& launch) {
+  const int H = A.H;
+  const int64_t per_set = (int64_t)A.n_chunk * H * RO_NPART * (int64_t)sizeof(double);
+  int64_t P_launch = ((int64_t)256 << 20) / per_set;
+  if (P_launch < 1) P_launch = 1;
+  if (P_launch > P) P_launch = P;
+  HIP_TRY(hipMalloc(&A.partials, (size_t)(per_set * P_launch)));
+  hipError_t el = hipSuccess;
+  for (int64_t p0 = 0; p0 < P && el == hipSuccess; p0 += P_launch) {
+    const int Pl = (int)(P - p0 < P_launch ? P - p0 : P_launch);
+    launch(A, dim3((unsigned)((int64_t)Pl * A.n_chunk)), (int)p0);
+    hipLaunchKernelGGL(tyre_rollout_finish_kernel, dim3((unsigned)(((int64_t)Pl * H + 63) / 64)), dim3(64), 0, st,
+                       (int)H, A.n_chunk, (const double*)A.partials, (int)p0, Pl, stats, count);
+    el = hipGetLastError();
+  }
+  hipError_t es = hipStreamSynchronize(st);
+  (void)hipFree(A.partials);
+  HIP_TRY(el);
+  HIP_TRY(es);
+  return MR_OK;
 }
 
 extern "C" {
@@ -963,32 +1005,18 @@ int mr_tyre_fit(const mr_tyrefit_config* cfg, int32_t n_train, const double* tra
   MR_GUARD_DEVICE(dev);
   hipStream_t st = (hipStream_t)hip_stream;
   // checking pass: no perm entry is dereferenced as a row index before it is known to be in range
-  int* bad_dev = nullptr;
   int bad = 0;
-  HIP_TRY(hipMalloc(&bad_dev, sizeof(int)));
-  hipError_t e0 = hipMemsetAsync(bad_dev, 0, sizeof(int), st);
-  const int64_t per_run = (int64_t)cfg->epochs * n_train;
-  const int R_perm = perm_stride_run ? R : 1;
-  const int64_t blocks = (per_run * R_perm + 255) / 256;
-  hipLaunchKernelGGL(tyre_perm_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, perm,
-                     per_run, R_perm, perm_stride_run, (int)n_train, bad_dev);
-  hipError_t e1 = hipGetLastError();
-  hipError_t e2 = hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, st);
-  hipError_t e3 = hipStreamSynchronize(st);
-  (void)hipFree(bad_dev);
-  HIP_TRY(e0);
-  HIP_TRY(e1);
-  HIP_TRY(e2);
-  HIP_TRY(e3);
+  const int rc = device_check(st, 1, &bad, [&](int* flag) {
+    const int64_t per_run = (int64_t)cfg->epochs * n_train;
+    const int R_perm = perm_stride_run ? R : 1;
+    const int64_t blocks = (per_run * R_perm + 255) / 256;
+    hipLaunchKernelGGL(tyre_perm_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, perm,
+                       per_run, R_perm, perm_stride_run, (int)n_train, flag);
+  });
+  if (rc != MR_OK) return rc;
   if (bad) return fail(MR_ERR_ARG, "perm entry out of range [0, n_train)");
-  TfFitArgs A;
-  A.cfg = *cfg;
-  A.n_train = n_train; A.n_val = n_val; A.R = R;
-  A.train = train; A.val = val; A.init = init; A.Fz = Fz; A.hyper = hyper;
-  A.perm = perm; A.perm_stride_run = perm_stride_run;
-  A.p_final = p_final; A.p_best = p_best; A.train_loss = train_loss; A.val_loss = val_loss; A.lr_hist = lr_hist;
-  A.flag = flag;
-  A.p_steps = p_steps;
+  const TfFitArgs A = make_tf_fit_args(*cfg, n_train, train, n_val, val, R, init, Fz, hyper, perm, perm_stride_run,
+                                       p_final, p_best, train_loss, val_loss, lr_hist, flag, p_steps);
   if (cfg->kind == MR_TYRE_PACEJKA)
     hipLaunchKernelGGL(tyre_fit_kernel<MR_TYRE_PACEJKA>, dim3((unsigned)R), dim3(64), 0, st, A);
   else
@@ -1019,53 +1047,20 @@ int mr_vehicle_step(const mr_tyrefit_config* cfg, int32_t n, const double* state
 int mr_tyre_rollout(const mr_tyrefit_config* cfg, int32_t T, const double* log, int32_t n_start, const int32_t* start,
                     int32_t H, int32_t P, const double* params, const double* Fz, double* stats, int32_t* count,
                     double* pred, void* hip_stream) {
-  if (const char* e = rollout_check(cfg, T, n_start, H, P)) return fail(MR_ERR_ARG, e);
+  if (const char* e = tyre_rollout_check(cfg, T, n_start, H, P)) return fail(MR_ERR_ARG, e);
   if (!log || !start || !params || !Fz || !stats || !count) return fail(MR_ERR_ARG, "null argument");
   int dev = -1;
   if (pointer_device(log, &dev) != 0) return fail(MR_ERR_ARG, "log is not a HIP device pointer");
   MR_GUARD_DEVICE(dev);
   hipStream_t st = (hipStream_t)hip_stream;
-  // checking pass: no start is used as a row index before it is known to be in range
-  int* bad_dev = nullptr;
+  const RoArgs A = make_ro_args(T, log, n_start, start, H, params, Fz, pred);
   int bad = 0;
-  HIP_TRY(hipMalloc(&bad_dev, sizeof(int)));
-  hipError_t e0 = hipMemsetAsync(bad_dev, 0, sizeof(int), st);
-  const int blocks = (n_start + 255) / 256;
-  hipLaunchKernelGGL(tyre_start_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, start,
-                     (int)n_start, (int)(T - 1 - H), bad_dev);
-  hipError_t e1 = hipGetLastError();
-  hipError_t e2 = hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, st);
-  hipError_t e3 = hipStreamSynchronize(st);
-  (void)hipFree(bad_dev);
-  HIP_TRY(e0);
-  HIP_TRY(e1);
-  HIP_TRY(e2);
-  HIP_TRY(e3);
+  const int rc = device_check(st, 1, &bad, [&](int* flag) { start_check_launch(st, A, flag); });
+  if (rc != MR_OK) return rc;
   if (bad) return fail(MR_ERR_ARG, "start entry out of range [0, T - 1 - H]");
-  RoArgs A;
-  A.cfg = *cfg;
-  A.T = T; A.n_start = n_start; A.H = H;
-  A.n_chunk = (n_start + WL - 1) / WL;
-  A.log = log; A.start = start; A.params = params; A.Fz = Fz; A.pred = pred;
-  // the partials of at most P_launch sets at a time (256 MiB): launches on one stream reuse the buffer in order
-  const int64_t per_set = (int64_t)A.n_chunk * H * RO_NPART * (int64_t)sizeof(double);
-  int64_t P_launch = ((int64_t)256 << 20) / per_set;
-  if (P_launch < 1) P_launch = 1;
-  if (P_launch > P) P_launch = P;
-  HIP_TRY(hipMalloc(&A.partials, (size_t)(per_set * P_launch)));
-  hipError_t el = hipSuccess;
-  for (int64_t p0 = 0; p0 < P && el == hipSuccess; p0 += P_launch) {
-    const int Pl = (int)(P - p0 < P_launch ? P - p0 : P_launch);
-    hipLaunchKernelGGL(tyre_rollout_kernel, dim3((unsigned)((int64_t)Pl * A.n_chunk)), dim3(64), 0, st, A, (int)p0);
-    hipLaunchKernelGGL(tyre_rollout_finish_kernel, dim3((unsigned)(((int64_t)Pl * H + 63) / 64)), dim3(64), 0, st,
-                       (int)H, A.n_chunk, (const double*)A.partials, (int)p0, Pl, stats, count);
-    el = hipGetLastError();
-  }
-  hipError_t es = hipStreamSynchronize(st);  // the partials buffer is released below
-  (void)hipFree(A.partials);
-  HIP_TRY(el);
-  HIP_TRY(es);
-  return MR_OK;
+  return rollout_launch(st, A, P, stats, count, [&](const RoArgs& Ap, dim3 grid, int p0) {
+    hipLaunchKernelGGL(tyre_rollout_kernel, grid, dim3(64), 0, st, *cfg, Ap, p0);
+  });
 }
 
 int mr_plant_params_default(double* params) {
@@ -1097,59 +1092,25 @@ int mr_plant_rollout(int32_t model, int32_t T, const double* log, int32_t n_star
   if (pointer_device(log, &dev) != 0) return fail(MR_ERR_ARG, "log is not a HIP device pointer");
   MR_GUARD_DEVICE(dev);
   hipStream_t st = (hipStream_t)hip_stream;
-  // checking pass: no start is used as a row index before it is known to be in range, and every fixed
-  // step is a positive finite number
-  int* bad_dev = nullptr;
+  const RoArgs A = make_ro_args(T, log, n_start, start, H, params, dt, pred);
+  // besides the starts, every fixed step must be a positive finite number
   int bad[2] = {0, 0};
-  HIP_TRY(hipMalloc(&bad_dev, 2 * sizeof(int)));
-  hipError_t e0 = hipMemsetAsync(bad_dev, 0, 2 * sizeof(int), st);
-  const int blocks = (n_start + 255) / 256;
-  hipLaunchKernelGGL(tyre_start_check_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, start,
-                     (int)n_start, (int)(T - 1 - H), bad_dev);
-  if (dt) {
-    const int bd = (P + 255) / 256;
-    hipLaunchKernelGGL(plant_dt_check_kernel, dim3((unsigned)(bd < 4096 ? bd : 4096)), dim3(256), 0, st, dt, (int)P,
-                       bad_dev + 1);
-  }
-  hipError_t e1 = hipGetLastError();
-  hipError_t e2 = hipMemcpyAsync(bad, bad_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-  hipError_t e3 = hipStreamSynchronize(st);
-  (void)hipFree(bad_dev);
-  HIP_TRY(e0);
-  HIP_TRY(e1);
-  HIP_TRY(e2);
-  HIP_TRY(e3);
+  const int rc = device_check(st, 2, bad, [&](int* flag) {
+    start_check_launch(st, A, flag);
+    if (dt) {
+      const int bd = (P + 255) / 256;
+      hipLaunchKernelGGL(plant_dt_check_kernel, dim3((unsigned)(bd < 4096 ? bd : 4096)), dim3(256), 0, st, dt, (int)P,
+                         flag + 1);
+    }
+  });
+  if (rc != MR_OK) return rc;
   if (bad[0]) return fail(MR_ERR_ARG, "start entry out of range [0, T - 1 - H]");
   if (bad[1]) return fail(MR_ERR_ARG, "dt entry not a positive finite number");
-  PrArgs A;
-  A.T = T; A.n_start = n_start; A.H = H;
-  A.n_chunk = (n_start + WL - 1) / WL;
-  A.log = log; A.start = start; A.params = params; A.dt = dt; A.pred = pred;
-  // the partials of at most P_launch sets at a time (256 MiB): launches on one stream reuse the buffer in order
-  const int64_t per_set = (int64_t)A.n_chunk * H * RO_NPART * (int64_t)sizeof(double);
-  int64_t P_launch = ((int64_t)256 << 20) / per_set;
-  if (P_launch < 1) P_launch = 1;
-  if (P_launch > P) P_launch = P;
-  HIP_TRY(hipMalloc(&A.partials, (size_t)(per_set * P_launch)));
-  hipError_t el = hipSuccess;
-  for (int64_t p0 = 0; p0 < P && el == hipSuccess; p0 += P_launch) {
-    const int Pl = (int)(P - p0 < P_launch ? P - p0 : P_launch);
-    const dim3 grid((unsigned)((int64_t)Pl * A.n_chunk));
-    if (model == MR_PLANT_KINEMATIC)
-      hipLaunchKernelGGL(plant_rollout_kernel<PLANT_KIN>, grid, dim3(64), 0, st, A, (int)p0);
-    else if (model == MR_PLANT_DYNAMIC)
-      hipLaunchKernelGGL(plant_rollout_kernel<PLANT_DYN>, grid, dim3(64), 0, st, A, (int)p0);
-    else
-      hipLaunchKernelGGL(plant_rollout_kernel<PLANT_BLEND>, grid, dim3(64), 0, st, A, (int)p0);
-    hipLaunchKernelGGL(tyre_rollout_finish_kernel, dim3((unsigned)(((int64_t)Pl * H + 63) / 64)), dim3(64), 0, st,
-                       (int)H, A.n_chunk, (const double*)A.partials, (int)p0, Pl, stats, count);
-    el = hipGetLastError();
-  }
-  hipError_t es = hipStreamSynchronize(st);  // the partials buffer is released below
-  (void)hipFree(A.partials);
-  HIP_TRY(el);
-  HIP_TRY(es);
-  return MR_OK;
+  return rollout_launch(st, A, P, stats, count, [&](const RoArgs& Ap, dim3 grid, int p0) {
+    plant_dispatch(model, [&](auto model_c) {
+      hipLaunchKernelGGL(plant_rollout_kernel<decltype(model_c)::value>, grid, dim3(64), 0, st, Ap, p0);
+    });
+  });
 }
 
 int mr_pid_gains_default(double* gains) {
@@ -1174,14 +1135,14 @@ int mr_pid_drive(const mr_track* tr, int32_t model, int32_t n, int32_t T, double
   if (!state || !mem || !gains || !params || !ticks_done) return fail(MR_ERR_ARG, "null argument");
   if (n == 0) return MR_OK;
   MR_GUARD_DEVICE(tr->device);
-  PidDriveArgs A;
-  A.n = n; A.T = T; A.G = G; A.P = P; A.dt = dt;
-  A.state = state; A.mem = mem; A.gains = gains; A.params = params;
-  A.log_mask = log_mask; A.log = log; A.ticks_done = ticks_done;
+  const PidDriveArgs A = make_pid_drive_args(n, T, dt, state, mem, G, gains, P, params, log_mask, log, ticks_done);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (model == MR_PLANT_KINEMATIC) pid_drive_launch<PLANT_KIN>(tr, A, st);
-  else if (model == MR_PLANT_DYNAMIC) pid_drive_launch<PLANT_DYN>(tr, A, st);
-  else pid_drive_launch<PLANT_BLEND>(tr, A, st);
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  plant_dispatch(model, [&](auto model_c) {
+    constexpr int MODEL = decltype(model_c)::value;
+    if (P == 1) hipLaunchKernelGGL((pid_drive_kernel<MODEL, true>), grid, block, 0, st, tr->view, A);
+    else hipLaunchKernelGGL((pid_drive_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
+  });
   HIP_TRY(hipGetLastError());
   return MR_OK;
 }
@@ -1195,14 +1156,14 @@ int mr_pid_segment_times(const mr_track* tr, int32_t model, int32_t n, int32_t K
     return fail(MR_ERR_ARG, "null argument");
   if (n == 0) return MR_OK;
   MR_GUARD_DEVICE(tr->device);
-  PidSegArgs A;
-  A.n = n; A.T = T; A.K = K; A.P = P; A.dt = dt;
-  A.start = start; A.s_start = s_start; A.s_end = s_end; A.gains = gains; A.params = params;
-  A.times = times; A.ticks_done = ticks_done;
+  const PidSegArgs A = make_pid_seg_args(n, K, T, dt, start, s_start, s_end, gains, P, params, times, ticks_done);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (model == MR_PLANT_KINEMATIC) pid_segment_launch<PLANT_KIN>(tr, A, st);
-  else if (model == MR_PLANT_DYNAMIC) pid_segment_launch<PLANT_DYN>(tr, A, st);
-  else pid_segment_launch<PLANT_BLEND>(tr, A, st);
+  const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+  plant_dispatch(model, [&](auto model_c) {
+    constexpr int MODEL = decltype(model_c)::value;
+    if (P == 1) hipLaunchKernelGGL((pid_segment_kernel<MODEL, true>), grid, block, 0, st, tr->view, A);
+    else hipLaunchKernelGGL((pid_segment_kernel<MODEL, false>), grid, block, 0, st, tr->view, A);
+  });
   HIP_TRY(hipGetLastError());
   return MR_OK;
 }
@@ -1226,14 +1187,8 @@ int mr_ga_breed(int32_t n_island, int32_t P, int32_t K, int32_t D, int32_t pairs
   int dev = -1;
   if (pointer_device(genes, &dev) != 0) return fail(MR_ERR_ARG, "genes is not a HIP device pointer");
   MR_GUARD_DEVICE(dev);
-  GaBreedArgs A;
-  A.n_island = n_island; A.P = P; A.K = K; A.D = D; A.pairs = pairs;
-  A.kT = kT; A.lambda_T = lambda_T; A.mutation_rate = mutation_rate;
-  A.seed = seed; A.island0 = island0; A.generation = generation;
-  A.ld = ld;
-  for (int d = 0; d < MR_GA_D_MAX; ++d) A.col[d] = col && d < D ? col[d] : d;
-  A.genes = genes; A.times = times; A.avg = avg; A.lo = lo; A.hi = hi;
-  A.r = r; A.best_r = best_r; A.best_idx = best_idx; A.best_genes = best_genes;
+  const GaBreedArgs A = make_ga_breed_args(n_island, P, K, D, pairs, genes, ld, col, times, avg, lo, hi, kT, lambda_T,
+                                           mutation_rate, seed, island0, generation, r, best_r, best_idx, best_genes);
   hipLaunchKernelGGL(ga_breed_kernel, dim3((unsigned)n_island), dim3(64), 0, (hipStream_t)hip_stream, A);
   HIP_TRY(hipGetLastError());
   return MR_OK;

@@ -21,25 +21,7 @@
 
 using namespace mr;
 
-template <typename T, int MODEL>
-struct Job {
-  const ProbParams<T>* P;
-  const mr_inputs* in;
-  const mr_outputs* out;
-  int64_t B, i;
-  T* ws;
-  T* lds;
-};
-
-template <typename T, int MODEL>
-static void wave_body(HostWave* hw, int lane, void* arg) {
-  Job<T, MODEL>* j = (Job<T, MODEL>*)arg;
-  Wv w{lane, hw};
-  solve_instance_wave<T, MODEL>(*j->P, *j->in, *j->out, j->B, j->i, j->ws, j->lds, w);
-  wsync(w);  // final rendezvous: every lane done before the wave is torn down
-}
-
-// Each instance runs as one emulated wavefront (64 fibers, mr_wave_prims.h) on one CPU thread.
+// Each instance runs as one emulated wavefront (64 fibers, mr_wave_prims.h host_wave_call) on one CPU thread.
 template <typename T, int MODEL>
 static void run(const mr_config& c, const TyreCoef<double>& tf, const TyreCoef<double>& tr, int B,
                 const mr_inputs& in, const mr_outputs& out, int nthreads) {
@@ -49,10 +31,9 @@ static void run(const mr_config& c, const TyreCoef<double>& tf, const TyreCoef<d
   for (int i = 0; i < B; ++i) {
     // poisoned workspace / LDS: any read-before-write shows up as NaN (device memory is not zeroed)
     std::vector<T> ws((size_t)ws_words<T>(), (T)NAN), lds((size_t)LDS_WORDS, (T)NAN);
-    Job<T, MODEL> job{&P, &in, &out, (int64_t)B, (int64_t)i, ws.data(), lds.data()};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &wave_body<T, MODEL>, &job);
-    delete hw;
+    host_wave_call([&](const Wv& w) {
+      solve_instance_wave<T, MODEL>(P, in, out, (int64_t)B, (int64_t)i, ws.data(), lds.data(), w);
+    });
   }
 }
 
@@ -70,6 +51,27 @@ static void run_scalar(const mr_config& c, const TyreCoef<double>& tf, const Tyr
 #pragma omp for schedule(dynamic, 1)
     for (int i = 0; i < B; ++i) solve_instance<T, MODEL>(P, in, out, (int64_t)B, (int64_t)i, WS<T>{ws.data(), 1});
   }
+}
+
+// The host side of every rollout (mr_rollout.h): the test of the starts' range, and the driver -- one emulated
+// wavefront per (set, chunk) running chunk(A, p, chunk, lds, w), the partials added in chunk order.
+static const char* rollout_starts_check(const RoArgs& A) {
+  for (int k = 0; k < A.n_start; ++k)
+    if (A.start[k] < 0 || A.start[k] > A.T - 1 - A.H) return "start entry out of range [0, T - 1 - H]";
+  return nullptr;
+}
+template <class Chunk>
+static void rollout_host(RoArgs A, int P, double* stats, int32_t* count, int nthreads, Chunk&& chunk) {
+  std::vector<double> partials((size_t)P * A.n_chunk * A.H * RO_NPART, NAN);
+  A.partials = partials.data();
+  const int64_t jobs = (int64_t)P * A.n_chunk;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
+  for (int64_t b = 0; b < jobs; ++b) {
+    std::vector<double> lds((size_t)RO_LDS_WORDS, NAN);
+    host_wave_call([&](const Wv& w) { chunk(A, (int)(b / A.n_chunk), (int)(b % A.n_chunk), lds.data(), w); });
+  }
+  for (int p = 0; p < P; ++p)
+    for (int k = 0; k < A.H; ++k) ro_finish(A.H, A.n_chunk, partials.data(), p, p, k, stats, count);
 }
 
 extern "C" {
@@ -271,18 +273,6 @@ int mrh_tyrefit_config_default(mr_tyrefit_config* c) {
   return 0;
 }
 
-struct LossGradJob {
-  const mr_tyrefit_config* cfg;
-  int n, p, chunk, n_chunk;
-  const double *rows, *params, *Fz;
-  double* partials;
-};
-static void lossgrad_body(HostWave* hw, int lane, void* arg) {
-  LossGradJob* j = (LossGradJob*)arg;
-  Wv w{lane, hw};
-  tf_lossgrad_chunk(w, *j->cfg, j->n, j->rows, j->p, j->chunk, j->n_chunk, j->params, j->Fz, j->partials);
-  wsync(w);
-}
 int mrh_tyre_loss_grad(const mr_tyrefit_config* cfg, int n, const double* rows, int P, const double* params,
                        const double* Fz, double* loss, double* grad) {
   if (const char* e = tyrefit_check_config(cfg)) return tyrefit_fail(e);
@@ -292,27 +282,14 @@ int mrh_tyre_loss_grad(const mr_tyrefit_config* cfg, int n, const double* rows, 
   const int n_chunk = (n + WL - 1) / WL;
   std::vector<double> partials((size_t)P * n_chunk * TF_NSUM, NAN);
   for (int p = 0; p < P; ++p)
-    for (int k = 0; k < n_chunk; ++k) {
-      LossGradJob job{cfg, n, p, k, n_chunk, rows, params, Fz, partials.data()};
-      HostWave* hw = new HostWave();
-      host_wave_run(*hw, &lossgrad_body, &job);
-      delete hw;
-    }
+    for (int k = 0; k < n_chunk; ++k)
+      host_wave_call([&](const Wv& w) {
+        tf_lossgrad_chunk(w, *cfg, n, rows, p, k, n_chunk, params, Fz, partials.data());
+      });
   for (int p = 0; p < P; ++p) tf_lossgrad_finish(*cfg, n, p, n_chunk, partials.data(), params, Fz, loss, grad);
   return 0;
 }
 
-struct FitJob {
-  const TfFitArgs* A;
-  int run;
-};
-static void fit_body(HostWave* hw, int lane, void* arg) {
-  FitJob* j = (FitJob*)arg;
-  Wv w{lane, hw};
-  if (j->A->cfg.kind == MR_TYRE_PACEJKA) tf_fit_run<MR_TYRE_PACEJKA>(*j->A, j->run, w);
-  else tf_fit_run<MR_TYRE_LINEAR>(*j->A, j->run, w);
-  wsync(w);
-}
 int mrh_tyre_fit(const mr_tyrefit_config* cfg, int n_train, const double* train, int n_val, const double* val, int R,
                  const double* init, const double* Fz, const double* hyper, const int32_t* perm,
                  int64_t perm_stride_run, double* p_final, double* p_best, double* train_loss, double* val_loss,
@@ -327,21 +304,14 @@ int mrh_tyre_fit(const mr_tyrefit_config* cfg, int n_train, const double* train,
       const int32_t v = perm[r * perm_stride_run + k];
       if (v < 0 || v >= n_train) return tyrefit_fail("perm entry out of range [0, n_train)");
     }
-  TfFitArgs A;
-  A.cfg = *cfg;
-  A.n_train = n_train; A.n_val = n_val; A.R = R;
-  A.train = train; A.val = val; A.init = init; A.Fz = Fz; A.hyper = hyper;
-  A.perm = perm; A.perm_stride_run = perm_stride_run;
-  A.p_final = p_final; A.p_best = p_best; A.train_loss = train_loss; A.val_loss = val_loss; A.lr_hist = lr_hist;
-  A.flag = flag;
-  A.p_steps = p_steps;
+  const TfFitArgs A = make_tf_fit_args(*cfg, n_train, train, n_val, val, R, init, Fz, hyper, perm, perm_stride_run,
+                                       p_final, p_best, train_loss, val_loss, lr_hist, flag, p_steps);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-  for (int r = 0; r < R; ++r) {
-    FitJob job{&A, r};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &fit_body, &job);
-    delete hw;
-  }
+  for (int r = 0; r < R; ++r)
+    host_wave_call([&](const Wv& w) {
+      if (A.cfg.kind == MR_TYRE_PACEJKA) tf_fit_run<MR_TYRE_PACEJKA>(A, r, w);
+      else tf_fit_run<MR_TYRE_LINEAR>(A, r, w);
+    });
   return 0;
 }
 
@@ -357,42 +327,16 @@ int mrh_vehicle_step(const mr_tyrefit_config* cfg, int n, const double* state, c
   return 0;
 }
 
-struct RolloutJob {
-  const RoArgs* A;
-  int p, chunk;
-  double* lds;
-};
-static void rollout_body(HostWave* hw, int lane, void* arg) {
-  RolloutJob* j = (RolloutJob*)arg;
-  Wv w{lane, hw};
-  ro_chunk_kind(*j->A, j->p, j->p, j->chunk, j->lds, w);
-  wsync(w);
-}
 int mrh_tyre_rollout(const mr_tyrefit_config* cfg, int T, const double* log, int n_start, const int32_t* start, int H,
                      int P, const double* params, const double* Fz, double* stats, int32_t* count, double* pred,
                      int nthreads) {
-  if (const char* e = rollout_check(cfg, T, n_start, H, P)) return tyrefit_fail(e);
+  if (const char* e = tyre_rollout_check(cfg, T, n_start, H, P)) return tyrefit_fail(e);
   if (!log || !start || !params || !Fz || !stats || !count) return tyrefit_fail("null argument");
-  for (int k = 0; k < n_start; ++k)
-    if (start[k] < 0 || start[k] > T - 1 - H) return tyrefit_fail("start entry out of range [0, T - 1 - H]");
-  RoArgs A;
-  A.cfg = *cfg;
-  A.T = T; A.n_start = n_start; A.H = H;
-  A.n_chunk = (n_start + WL - 1) / WL;
-  A.log = log; A.start = start; A.params = params; A.Fz = Fz; A.pred = pred;
-  std::vector<double> partials((size_t)P * A.n_chunk * H * RO_NPART, NAN);
-  A.partials = partials.data();
-  const int64_t jobs = (int64_t)P * A.n_chunk;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-  for (int64_t b = 0; b < jobs; ++b) {
-    std::vector<double> lds((size_t)RO_LDS_WORDS, NAN);
-    RolloutJob job{&A, (int)(b / A.n_chunk), (int)(b % A.n_chunk), lds.data()};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &rollout_body, &job);
-    delete hw;
-  }
-  for (int p = 0; p < P; ++p)
-    for (int k = 0; k < H; ++k) ro_finish(H, A.n_chunk, partials.data(), p, p, k, stats, count);
+  const RoArgs A = make_ro_args(T, log, n_start, start, H, params, Fz, pred);
+  if (const char* e = rollout_starts_check(A)) return tyrefit_fail(e);
+  rollout_host(A, P, stats, count, nthreads, [&](const RoArgs& Ap, int p, int chunk, double* lds, const Wv& w) {
+    ro_chunk_kind(*cfg, Ap, p, p, chunk, lds, w);
+  });
   return 0;
 }
 
@@ -409,45 +353,20 @@ int mrh_plant_step_params(int model, int n, const double* state, const double* c
   return 0;
 }
 
-struct PlantRolloutJob {
-  const PrArgs* A;
-  int model, p, chunk;
-  double* lds;
-};
-static void plant_rollout_body(HostWave* hw, int lane, void* arg) {
-  PlantRolloutJob* j = (PlantRolloutJob*)arg;
-  Wv w{lane, hw};
-  if (j->model == PLANT_KIN) pr_chunk<PLANT_KIN>(*j->A, j->p, j->p, j->chunk, j->lds, w);
-  else if (j->model == PLANT_DYN) pr_chunk<PLANT_DYN>(*j->A, j->p, j->p, j->chunk, j->lds, w);
-  else pr_chunk<PLANT_BLEND>(*j->A, j->p, j->p, j->chunk, j->lds, w);
-  wsync(w);
-}
 int mrh_plant_rollout(int model, int T, const double* log, int n_start, const int32_t* start, int H, int P,
                       const double* params, const double* dt, double* stats, int32_t* count, double* pred,
                       int nthreads) {
   if (const char* e = plant_rollout_check(model, T, n_start, H, P)) return tyrefit_fail(e);
   if (!log || !start || !params || !stats || !count) return tyrefit_fail("null argument");
-  for (int k = 0; k < n_start; ++k)
-    if (start[k] < 0 || start[k] > T - 1 - H) return tyrefit_fail("start entry out of range [0, T - 1 - H]");
+  const RoArgs A = make_ro_args(T, log, n_start, start, H, params, dt, pred);
+  if (const char* e = rollout_starts_check(A)) return tyrefit_fail(e);
   for (int p = 0; dt && p < P; ++p)
     if (!plant_dt_ok(dt[p])) return tyrefit_fail("dt entry not a positive finite number");
-  PrArgs A;
-  A.T = T; A.n_start = n_start; A.H = H;
-  A.n_chunk = (n_start + WL - 1) / WL;
-  A.log = log; A.start = start; A.params = params; A.dt = dt; A.pred = pred;
-  std::vector<double> partials((size_t)P * A.n_chunk * H * RO_NPART, NAN);
-  A.partials = partials.data();
-  const int64_t jobs = (int64_t)P * A.n_chunk;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-  for (int64_t b = 0; b < jobs; ++b) {
-    std::vector<double> lds((size_t)RO_LDS_WORDS, NAN);
-    PlantRolloutJob job{&A, model, (int)(b / A.n_chunk), (int)(b % A.n_chunk), lds.data()};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &plant_rollout_body, &job);
-    delete hw;
-  }
-  for (int p = 0; p < P; ++p)
-    for (int k = 0; k < H; ++k) ro_finish(H, A.n_chunk, partials.data(), p, p, k, stats, count);
+  plant_dispatch(model, [&](auto model_c) {
+    rollout_host(A, P, stats, count, nthreads, [&](const RoArgs& Ap, int p, int chunk, double* lds, const Wv& w) {
+      ro_chunk(Ap, RoPlantModel<decltype(model_c)::value>(Ap, p), p, p, chunk, lds, w);
+    });
+  });
   return 0;
 }
 
@@ -479,17 +398,13 @@ int mrh_pid_drive(const double* blob, int nt, double L, int n_rows, int model, i
   if (const char* e = pid_drive_check(model, n, T, dt, G, P, log_mask, log)) return tyrefit_fail(e);
   if (!blob || !state || !mem || !gains || !params || !ticks_done) return tyrefit_fail("null argument");
   const TrackView Tr = track_view(blob, nt, L, n_rows);
-  PidDriveArgs A;
-  A.n = n; A.T = T; A.G = G; A.P = P; A.dt = dt;
-  A.state = state; A.mem = mem; A.gains = gains; A.params = params;
-  A.log_mask = log_mask; A.log = log; A.ticks_done = ticks_done;
+  const PidDriveArgs A = make_pid_drive_args(n, T, dt, state, mem, G, gains, P, params, log_mask, log, ticks_done);
+  plant_dispatch(model, [&](auto model_c) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-  for (int i = 0; i < n; ++i) {
-    const double* q = params + (int64_t)(P == 1 ? 0 : i) * MR_PLANT_NPAR;
-    if (model == PLANT_KIN) pid_drive_vehicle<PLANT_KIN>(Tr, A, i, true, q, PidVoteLane());
-    else if (model == PLANT_DYN) pid_drive_vehicle<PLANT_DYN>(Tr, A, i, true, q, PidVoteLane());
-    else pid_drive_vehicle<PLANT_BLEND>(Tr, A, i, true, q, PidVoteLane());
-  }
+    for (int i = 0; i < n; ++i)
+      pid_drive_vehicle<decltype(model_c)::value>(Tr, A, i, true, params + (int64_t)(P == 1 ? 0 : i) * MR_PLANT_NPAR,
+                                                  PidVoteLane());
+  });
   return 0;
 }
 
@@ -501,17 +416,13 @@ int mrh_pid_segment_times(const double* blob, int nt, double L, int n_rows, int 
   if (!blob || !start || !s_start || !s_end || !gains || !params || !times || !ticks_done)
     return tyrefit_fail("null argument");
   const TrackView Tr = track_view(blob, nt, L, n_rows);
-  PidSegArgs A;
-  A.n = n; A.T = T; A.K = K; A.P = P; A.dt = dt;
-  A.start = start; A.s_start = s_start; A.s_end = s_end; A.gains = gains; A.params = params;
-  A.times = times; A.ticks_done = ticks_done;
+  const PidSegArgs A = make_pid_seg_args(n, K, T, dt, start, s_start, s_end, gains, P, params, times, ticks_done);
+  plant_dispatch(model, [&](auto model_c) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-  for (int i = 0; i < n; ++i) {
-    const double* q = params + (int64_t)(P == 1 ? 0 : i) * MR_PLANT_NPAR;
-    if (model == PLANT_KIN) pid_segment_vehicle<PLANT_KIN>(Tr, A, i, true, q, PidVoteLane());
-    else if (model == PLANT_DYN) pid_segment_vehicle<PLANT_DYN>(Tr, A, i, true, q, PidVoteLane());
-    else pid_segment_vehicle<PLANT_BLEND>(Tr, A, i, true, q, PidVoteLane());
-  }
+    for (int i = 0; i < n; ++i)
+      pid_segment_vehicle<decltype(model_c)::value>(Tr, A, i, true, params + (int64_t)(P == 1 ? 0 : i) * MR_PLANT_NPAR,
+                                                    PidVoteLane());
+  });
   return 0;
 }
 int mrh_ga_random(uint64_t seed, uint64_t island, uint64_t generation, uint64_t first, int64_t count, uint64_t* out) {
@@ -521,17 +432,6 @@ int mrh_ga_random(uint64_t seed, uint64_t island, uint64_t generation, uint64_t 
   for (int64_t j = 0; j < count; ++j) out[j] = rs.raw(first + (uint64_t)j);
   return 0;
 }
-struct BreedJob {
-  const GaBreedArgs* A;
-  int island;
-  GaShared* sh;
-};
-static void breed_body(HostWave* hw, int lane, void* arg) {
-  BreedJob* j = (BreedJob*)arg;
-  Wv w{lane, hw};
-  ga_breed_island(w, *j->A, j->island, j->sh);
-  wsync(w);
-}
 int mrh_ga_breed(int n_island, int P, int K, int D, int pairs, double* genes, int ld, const int32_t* col,
                  const double* times, double* avg,
                  const double* lo, const double* hi, double kT, double lambda_T, double mutation_rate, uint64_t seed,
@@ -539,20 +439,11 @@ int mrh_ga_breed(int n_island, int P, int K, int D, int pairs, double* genes, in
                  double* best_genes) {
   if (const char* e = ga_breed_check(n_island, P, K, D, pairs, ld, col, kT, lambda_T, mutation_rate)) return tyrefit_fail(e);
   if (!genes || !times || !avg || !r || !best_r || !best_idx || !best_genes) return tyrefit_fail("null argument");
-  GaBreedArgs A;
-  A.n_island = n_island; A.P = P; A.K = K; A.D = D; A.pairs = pairs;
-  A.kT = kT; A.lambda_T = lambda_T; A.mutation_rate = mutation_rate;
-  A.seed = seed; A.island0 = island0; A.generation = generation;
-  A.ld = ld;
-  for (int d = 0; d < MR_GA_D_MAX; ++d) A.col[d] = col && d < D ? col[d] : d;
-  A.genes = genes; A.times = times; A.avg = avg; A.lo = lo; A.hi = hi;
-  A.r = r; A.best_r = best_r; A.best_idx = best_idx; A.best_genes = best_genes;
+  const GaBreedArgs A = make_ga_breed_args(n_island, P, K, D, pairs, genes, ld, col, times, avg, lo, hi, kT, lambda_T,
+                                           mutation_rate, seed, island0, generation, r, best_r, best_idx, best_genes);
   for (int i = 0; i < n_island; ++i) {
     GaShared* sh = new GaShared();
-    BreedJob job{&A, i, sh};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &breed_body, &job);
-    delete hw;
+    host_wave_call([&](const Wv& w) { ga_breed_island(w, A, i, sh); });
     delete sh;
   }
   return 0;
@@ -563,51 +454,15 @@ int mrh_ga_breed(int n_island, int P, int K, int D, int pairs, double* genes, in
 // ---- probes of the wave primitives and the fp32 pieces (mr_probe.h): the bodies that
 // libmpcracing_probe.so runs on gfx950, here under the fibre emulation / with libm ----
 template <typename T>
-struct PrimsJob {
-  int wg, n_wg;
-  T* in;
-  T* out;
-};
-template <typename T>
-static void prims_wave_body(HostWave* hw, int lane, void* arg) {
-  PrimsJob<T>* j = (PrimsJob<T>*)arg;
-  Wv w{lane, hw};
-  probe::prims_body<T>(w, j->wg, j->n_wg, j->in, j->out);
-  wsync(w);
-}
-template <typename T>
 static int run_prims_host(int n_wg, T* in, T* out) {
   if (n_wg < 1 || !in || !out) return -1;
-  for (int g = 0; g < n_wg; ++g) {
-    PrimsJob<T> job{g, n_wg, in, out};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &prims_wave_body<T>, &job);
-    delete hw;
-  }
+  for (int g = 0; g < n_wg; ++g) host_wave_call([&](const Wv& w) { probe::prims_body<T>(w, g, n_wg, in, out); });
   return 0;
-}
-template <typename T>
-struct MfmaJob {
-  int wg;
-  const T *A, *B, *C;
-  T* D;
-};
-template <typename T>
-static void mfma_wave_body(HostWave* hw, int lane, void* arg) {
-  MfmaJob<T>* j = (MfmaJob<T>*)arg;
-  Wv w{lane, hw};
-  probe::mfma_body<T>(w, j->wg, j->A, j->B, j->C, j->D);
-  wsync(w);
 }
 template <typename T>
 static int run_mfma_host(int n_wg, const T* A, const T* B, const T* C, T* D) {
   if (n_wg < 1 || !A || !B || !C || !D) return -1;
-  for (int g = 0; g < n_wg; ++g) {
-    MfmaJob<T> job{g, A, B, C, D};
-    HostWave* hw = new HostWave();
-    host_wave_run(*hw, &mfma_wave_body<T>, &job);
-    delete hw;
-  }
+  for (int g = 0; g < n_wg; ++g) host_wave_call([&](const Wv& w) { probe::mfma_body<T>(w, g, A, B, C, D); });
   return 0;
 }
 

@@ -73,6 +73,17 @@ struct GaBreedArgs {
   int32_t* best_idx;    // [n_island]
   double* best_genes;   // [n_island][D], as they were before the replacement
 };
+// col null: gene d is column d
+inline GaBreedArgs make_ga_breed_args(int n_island, int P, int K, int D, int pairs, double* genes, int ld,
+                                      const int32_t* col, const double* times, double* avg, const double* lo,
+                                      const double* hi, double kT, double lambda_T, double mutation_rate,
+                                      uint64_t seed, uint64_t island0, uint64_t generation, double* r, double* best_r,
+                                      int32_t* best_idx, double* best_genes) {
+  GaBreedArgs A{n_island, P, K, D, pairs, kT, lambda_T, mutation_rate, seed, island0, generation, genes, ld, {},
+                times, avg, lo, hi, r, best_r, best_idx, best_genes};
+  for (int d = 0; d < MR_GA_D_MAX; ++d) A.col[d] = col && d < D ? col[d] : d;
+  return A;
+}
 
 inline const char* ga_breed_check(int64_t n_island, int64_t P, int64_t K, int64_t D, int64_t pairs, int64_t ld,
                                   const int32_t* col, double kT, double lambda_T, double mutation_rate) {

@@ -98,6 +98,25 @@ struct PidDriveArgs {
   double* log;           // [popcount(log_mask)][T][n]
   int32_t* ticks_done;   // [n]
 };
+inline PidDriveArgs make_pid_drive_args(int n, int T, double dt, double* state, double* mem, int G,
+                                        const double* gains, int P, const double* params, uint32_t log_mask,
+                                        double* log, int32_t* ticks_done) {
+  return PidDriveArgs{n, T, G, P, dt, state, mem, gains, params, log_mask, log, ticks_done};
+}
+
+// the tests a drive and a segment timing share, in the order both make them
+inline const char* pid_vehicles_check(int64_t model, int64_t n) {
+  if (model < PLANT_KIN || model > PLANT_BLEND) return "unknown plant model";
+  if (n < 0) return "n < 0";
+  if (n > (int64_t)0x7fffffff / MR_PID_NLOG) return "too many vehicles";
+  return nullptr;
+}
+inline const char* pid_ticks_check(int64_t T, double dt, const char* too_many) {
+  if (T < 1) return "T < 1";
+  if (T > MR_PID_T_MAX) return too_many;
+  if (!plant_dt_ok(dt)) return "dt must be a positive finite number";
+  return nullptr;
+}
 
 inline const char* pid_control_check(int64_t n, int64_t G, double dt) {
   if (n < 0) return "n < 0";
@@ -108,12 +127,8 @@ inline const char* pid_control_check(int64_t n, int64_t G, double dt) {
 }
 inline const char* pid_drive_check(int64_t model, int64_t n, int64_t T, double dt, int64_t G, int64_t P,
                                    uint32_t log_mask, const void* log) {
-  if (model < PLANT_KIN || model > PLANT_BLEND) return "unknown plant model";
-  if (n < 0) return "n < 0";
-  if (n > (int64_t)0x7fffffff / MR_PID_NLOG) return "too many vehicles";
-  if (T < 1) return "T < 1";
-  if (T > MR_PID_T_MAX) return "T > 4096 (a longer drive is several calls)";
-  if (!plant_dt_ok(dt)) return "dt must be a positive finite number";
+  if (const char* e = pid_vehicles_check(model, n)) return e;
+  if (const char* e = pid_ticks_check(T, dt, "T > 4096 (a longer drive is several calls)")) return e;
   if (G != 1 && G != n) return "G must be 1 (shared gains) or n (one vector per vehicle)";
   if (P != 1 && P != n) return "P must be 1 (shared parameters) or n (one vector per vehicle)";
   if (log_mask >> MR_PID_NLOG) return "log_mask has bits at or above MR_PID_NLOG";
@@ -126,12 +141,42 @@ struct PidVoteLane {
   MR_HD bool operator()(bool alive) const { return alive; }
 };
 
-// T ticks of vehicle i: pid_control -> plant_step<MODEL>(q, x, cmd_throttle - cmd_brake, cmd_steer, dt), the
-// tick's rows stored as log[row][t][i].  State, memory and gains stay in registers across the ticks; q points
-// at the vehicle's parameters (the caller's registers when they are shared).  A vehicle whose state, command
-// or next state is not finite stops before that tick: its rows from there on are NaN, state and mem keep the
-// values the tick started from, ticks_done is the number of ticks before it.  any_alive(alive) is true while
-// some lane of the wave still drives (the only cross-lane step); idle lanes (active false) store nothing.
+// The loop of every drive: up to T ticks of pid_control -> plant_step<MODEL>(q, x, cmd_throttle - cmd_brake,
+// cmd_steer, dt) from state x and memory m, which stay in registers across the ticks, as do the gains g; q points
+// at the vehicle's parameters (the caller's registers when they are shared).  A vehicle whose state, command or
+// next state is not finite stops before that tick: x and m keep the values the tick started from.  Per tick,
+// after that test and before x and m take the tick's result, hook(t, alive, x, o) sees the state the tick
+// started from and the agent's outputs; when it returns true the vehicle is finished after this tick (which
+// still counts).  any_alive(alive) is true while some lane of the wave still drives (the only cross-lane step).
+// Returns the number of ticks driven; *t_end (when given) is the tick at which the loop ended.
+template <int MODEL, class Vote, class Hook>
+MR_HD int pid_loop(const TrackView& Tr, const double* q, const double* g, double dt, int T, bool active, double* x,
+                   double* m, const Vote& any_alive, Hook&& hook, int* t_end) {
+  bool alive = active;
+  int done = 0;
+  int t = 0;
+  for (; t < T; ++t) {
+    if (!any_alive(alive)) break;
+    double mn[MR_PID_NMEM], o[MR_PID_NOUT], xn[6];
+    for (int c = 0; c < MR_PID_NMEM; ++c) mn[c] = m[c];
+    pid_control(Tr, x, mn, g, dt, o);
+    plant_step<MODEL>(q, x, o[2] - o[4], o[3], dt, xn);
+    bool ok = tf_finite(o[2]) && tf_finite(o[3]) && tf_finite(o[4]);
+    for (int c = 0; c < 6; ++c) ok = ok && tf_finite(x[c]) && tf_finite(xn[c]);
+    alive = alive && ok;
+    const bool finished = hook(t, alive, x, o);
+    for (int c = 0; c < 6; ++c) x[c] = alive ? xn[c] : x[c];
+    for (int c = 0; c < MR_PID_NMEM; ++c) m[c] = alive ? mn[c] : m[c];
+    done += alive ? 1 : 0;
+    alive = alive && !finished;
+  }
+  if (t_end) *t_end = t;
+  return done;
+}
+
+// T ticks of vehicle i with the tick's rows stored as log[row][t][i]: the rows of a stopped vehicle are NaN from
+// the tick at which it stopped, ticks_done is the number of ticks before it; idle lanes (active false) store
+// nothing.
 template <int MODEL, class Vote>
 MR_HD void pid_drive_vehicle(const TrackView& Tr, const PidDriveArgs& A, int i, bool active, const double* q,
                              const Vote& any_alive) {
@@ -142,33 +187,24 @@ MR_HD void pid_drive_vehicle(const TrackView& Tr, const PidDriveArgs& A, int i, 
   for (int c = 0; c < 6; ++c) x[c] = A.state[(int64_t)c * n + iv];
   for (int c = 0; c < MR_PID_NMEM; ++c) m[c] = A.mem[(int64_t)c * n + iv];
   for (int c = 0; c < MR_PID_NGAIN; ++c) g[c] = gp[c];
-  bool alive = active;
-  int done = 0;
-  int t = 0;
-  for (; t < A.T; ++t) {
-    if (!any_alive(alive)) break;
-    double mn[MR_PID_NMEM], o[MR_PID_NOUT], xn[6];
-    for (int c = 0; c < MR_PID_NMEM; ++c) mn[c] = m[c];
-    pid_control(Tr, x, mn, g, A.dt, o);
-    plant_step<MODEL>(q, x, o[2] - o[4], o[3], A.dt, xn);
-    bool ok = tf_finite(o[2]) && tf_finite(o[3]) && tf_finite(o[4]);
-    for (int c = 0; c < 6; ++c) ok = ok && tf_finite(x[c]) && tf_finite(xn[c]);
-    alive = alive && ok;
-    if (active && A.log_mask) {
-      double* lp = A.log + (int64_t)t * n + i;
-      const int64_t row = (int64_t)A.T * n;
+  int t;
+  const int done = pid_loop<MODEL>(
+      Tr, q, g, A.dt, A.T, active, x, m, any_alive,
+      [&](int tick, bool live, const double* xs, const double* o) {
+        if (active && A.log_mask) {
+          double* lp = A.log + (int64_t)tick * n + i;
+          const int64_t row = (int64_t)A.T * n;
 #pragma unroll
-      for (int r = 0; r < MR_PID_NLOG; ++r) {  // the mask is wave-uniform
-        if (!((A.log_mask >> r) & 1u)) continue;
-        const double v = r < 6 ? x[r] : (r == 6 ? o[7] : o[r - 7]);
-        *lp = alive ? v : NAN;
-        lp += row;
-      }
-    }
-    for (int c = 0; c < 6; ++c) x[c] = alive ? xn[c] : x[c];
-    for (int c = 0; c < MR_PID_NMEM; ++c) m[c] = alive ? mn[c] : m[c];
-    done += alive ? 1 : 0;
-  }
+          for (int r = 0; r < MR_PID_NLOG; ++r) {  // the mask is wave-uniform
+            if (!((A.log_mask >> r) & 1u)) continue;
+            const double v = r < 6 ? xs[r] : (r == 6 ? o[7] : o[r - 7]);
+            *lp = live ? v : NAN;
+            lp += row;
+          }
+        }
+        return false;
+      },
+      &t);
   if (!active) return;
   for (; t < A.T && A.log_mask; ++t) {  // the loop ended early: every lane of the wave had stopped
     double* lp = A.log + (int64_t)t * n + i;
@@ -195,22 +231,23 @@ struct PidSegArgs {
   double* times;          // [n]
   int32_t* ticks_done;    // [n]
 };
+inline PidSegArgs make_pid_seg_args(int n, int K, int T, double dt, const double* start, const double* s_start,
+                                    const double* s_end, const double* gains, int P, const double* params,
+                                    double* times, int32_t* ticks_done) {
+  return PidSegArgs{n, T, K, P, dt, start, s_start, s_end, gains, params, times, ticks_done};
+}
 
 inline const char* pid_segment_check(int64_t model, int64_t n, int64_t K, int64_t T, double dt, int64_t P) {
-  if (model < PLANT_KIN || model > PLANT_BLEND) return "unknown plant model";
-  if (n < 0) return "n < 0";
-  if (n > (int64_t)0x7fffffff / MR_PID_NLOG) return "too many vehicles";
+  if (const char* e = pid_vehicles_check(model, n)) return e;
   if (K < 1) return "K < 1";
   if (n % K != 0) return "n must be a multiple of K (vehicle i drives segment i % K with gains row i / K)";
-  if (T < 1) return "T < 1";
-  if (T > MR_PID_T_MAX) return "T > 4096";
-  if (!plant_dt_ok(dt)) return "dt must be a positive finite number";
+  if (const char* e = pid_ticks_check(T, dt, "T > 4096")) return e;
   if (P != 1 && P != n) return "P must be 1 (shared parameters) or n (one vector per vehicle)";
   return nullptr;
 }
 
-// The drive of pid_drive_vehicle without a log: vehicle i starts segment i % K with gains row i / K, and every
-// tick takes from its sensed progress what ga.crossing_times takes from the progress row: travelled =
+// The drive of pid_loop without a log: vehicle i starts segment i % K with gains row i / K, and every tick
+// takes from its sensed progress what ga.crossing_times takes from the progress row: travelled =
 // py_mod(progress - s_start, L), minus L above L / 2; at the first tick k with travelled >= need =
 // py_mod(s_end - s_start, L) the time is dt ((k - 1) + (need - a) / (c - a)), a and c the previous and the
 // current travelled; inf when k is 0; a NaN progress never hits.  A vehicle that has its time or has stopped (the
@@ -228,28 +265,18 @@ MR_HD void pid_segment_vehicle(const TrackView& Tr, const PidSegArgs& A, int i, 
   m[0] = s_start; m[1] = 0; m[2] = 0; m[3] = NAN;
   for (int c = 0; c < MR_PID_NGAIN; ++c) g[c] = gp[c];
   const double L = Tr.L, need = py_mod(A.s_end[seg] - s_start, L);
-  bool alive = active;
-  int done = 0;
   double tm = INFINITY, prev = 0;
-  for (int t = 0; t < A.T; ++t) {
-    if (!any_alive(alive)) break;
-    double mn[MR_PID_NMEM], o[MR_PID_NOUT], xn[6];
-    for (int c = 0; c < MR_PID_NMEM; ++c) mn[c] = m[c];
-    pid_control(Tr, x, mn, g, A.dt, o);
-    plant_step<MODEL>(q, x, o[2] - o[4], o[3], A.dt, xn);
-    bool ok = tf_finite(o[2]) && tf_finite(o[3]) && tf_finite(o[4]);
-    for (int c = 0; c < 6; ++c) ok = ok && tf_finite(x[c]) && tf_finite(xn[c]);
-    alive = alive && ok;
-    double tr = py_mod(o[0] - s_start, L);
-    tr = tr > 0.5 * L ? tr - L : tr;
-    const bool hit = alive && tr >= need;
-    if (hit && t > 0) tm = A.dt * ((double)(t - 1) + (need - prev) / (tr - prev));
-    prev = tr;
-    for (int c = 0; c < 6; ++c) x[c] = alive ? xn[c] : x[c];
-    for (int c = 0; c < MR_PID_NMEM; ++c) m[c] = alive ? mn[c] : m[c];
-    done += alive ? 1 : 0;
-    alive = alive && !hit;
-  }
+  const int done = pid_loop<MODEL>(
+      Tr, q, g, A.dt, A.T, active, x, m, any_alive,
+      [&](int tick, bool live, const double*, const double* o) {
+        double tr = py_mod(o[0] - s_start, L);
+        tr = tr > 0.5 * L ? tr - L : tr;
+        const bool hit = live && tr >= need;
+        if (hit && tick > 0) tm = A.dt * ((double)(tick - 1) + (need - prev) / (tr - prev));
+        prev = tr;
+        return hit;
+      },
+      nullptr);
   if (!active) return;
   A.times[i] = tm;
   A.ticks_done[i] = done;

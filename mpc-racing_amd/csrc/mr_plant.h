@@ -7,6 +7,7 @@
 // atan2(sin, cos), the kinematic yaw integrated with the new tan(delta) rate, and the true pi in
 // deg2rad.  Evaluation order follows the Python expressions term by term.
 #pragma once
+#include <type_traits>
 #include "mr_common.h"
 
 namespace mr {
@@ -211,6 +212,16 @@ MR_HD void plant_step(int model, const double* q, const double* x, double thr, d
   if (model == PLANT_KIN) plant_step<PLANT_KIN>(q, x, thr, steer, Ts, o);
   else if (model == PLANT_DYN) plant_step<PLANT_DYN>(q, x, thr, steer, Ts, o);
   else plant_step<PLANT_BLEND>(q, x, thr, steer, Ts, o);
+}
+
+// Host side: f(std::integral_constant<int, PLANT_*>()) for a checked run-time model -- the one place where a
+// launch or a host loop picks the instantiation of a kernel or wave body templated on the model (rollout,
+// drive, segment timing; mpcracing.hip and the host build).
+template <class F>
+inline void plant_dispatch(int model, F&& f) {
+  if (model == PLANT_KIN) f(std::integral_constant<int, PLANT_KIN>());
+  else if (model == PLANT_DYN) f(std::integral_constant<int, PLANT_DYN>());
+  else f(std::integral_constant<int, PLANT_BLEND>());
 }
 
 }  // namespace mr

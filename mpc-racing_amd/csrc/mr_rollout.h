@@ -2,7 +2,13 @@
 // statistics, and the model as a closed-loop plant (learning/compare.py:60, script/verify_dynamic.py,
 // script/test_model_error.py; learning/vehicle.py:136-205 iterated), fp64, host + gfx950.
 //
-// The model is tf_row<false> of mr_tyrefit.h, the tyre constants tf_tyres (with its double-double
+// The wave body, ro_chunk<Model>, is written once for every rollout (this one and the plant's, mr_plantroll.h):
+// start gather, finite test, the prefetch of the next step's controls and truth, the pred store, the 25
+// statistics and their reduction, the partials store and the "stopped lane keeps its state" commit.  A model
+// object supplies the step from (x, RoStep) to o and whether the yaw error is wrapped: RoTyreModel below,
+// RoPlantModel there.  RoArgs holds every rollout's arguments, make_ro_args fills them, rollout_check tests them.
+//
+// The tyre model is tf_row<false> of mr_tyrefit.h, the tyre constants tf_tyres (with its double-double
 // angle), prepared once per wave.  Rollout: one 64-lane wavefront per (parameter set, chunk of 64
 // start rows), one lane per start.  The log is structure-of-arrays [9][T]: X, Y, yaw, vx, vy,
 // yawdot, throttle (cmd_throttle - cmd_brake), steer, ts, where ts[i] is the duration of the tick
@@ -33,19 +39,24 @@ namespace mr {
 constexpr int RO_NLOG = 9;    // rows of the log
 constexpr int RO_NPART = 25;  // per step: 6 x (sum e, sum e^2, min, max), then the count
 
+// The arguments of every rollout.  The tyre rollout passes its mr_tyrefit_config beside them; in the kernels'
+// argument blocks every field sits where it sat when the two rollouts had a struct each.
 struct RoArgs {
-  mr_tyrefit_config cfg;
   int T, n_start, H, n_chunk;
-  const double* log;     // [9][T]
-  const int32_t* start;  // [n_start], every entry in [0, T - 1 - H] (checked before the launch)
-  const double* params;  // [P][n_par]
-  const double* Fz;      // [P][2]
-  double* partials;      // [sets of the launch][n_chunk][H][25]
-  double* pred;          // optional [P][H][6][n_start]
+  const double* log;      // [9][T]
+  const int32_t* start;   // [n_start], every entry in [0, T - 1 - H] (checked before the launch)
+  const double* params;   // [P][parameters of the model]
+  const double* per_set;  // the model's second array: the tyres' Fz [P][2]; the plant's dt [P] or null (ts of the log)
+  double* partials;       // [sets of the launch][n_chunk][H][25], set by the driver of the launch
+  double* pred;           // optional [P][H][6][n_start]
 };
+inline RoArgs make_ro_args(int T, const double* log, int n_start, const int32_t* start, int H, const double* params,
+                           const double* per_set, double* pred) {
+  return RoArgs{T, n_start, H, (n_start + WL - 1) / WL, log, start, params, per_set, nullptr, pred};
+}
 
-inline const char* rollout_check(const mr_tyrefit_config* c, int64_t T, int64_t n_start, int64_t H, int64_t P) {
-  if (const char* e = tyrefit_check_config(c)) return e;
+// the tests every rollout's sizes pass (a model checks its own arguments before them)
+inline const char* rollout_check(int64_t T, int64_t n_start, int64_t H, int64_t P) {
   if (T < 2) return "T < 2";
   if (T > (int64_t)0x7fffffff / RO_NLOG) return "too many log rows";
   if (n_start < 1) return "n_start < 1";
@@ -54,6 +65,10 @@ inline const char* rollout_check(const mr_tyrefit_config* c, int64_t T, int64_t 
   if (P < 1) return "P < 1";
   if (P * ((n_start + WL - 1) / WL) > (int64_t)0x7fffffff) return "P * ceil(n_start / 64) exceeds the grid limit";
   return nullptr;
+}
+inline const char* tyre_rollout_check(const mr_tyrefit_config* c, int64_t T, int64_t n_start, int64_t H, int64_t P) {
+  if (const char* e = tyrefit_check_config(c)) return e;
+  return rollout_check(T, n_start, H, P);
 }
 
 constexpr int RO_LDS_WORDS = MR_ROLLOUT_STATS ? WL * RO_NPART : 1;  // doubles of LDS per wave
@@ -91,19 +106,40 @@ MR_HD void ro_load(const double* log, int T, int s, int k, RoStep* r) {
   for (int c = 0; c < 6; ++c) r->truth[c] = log[(int64_t)c * T + i];
 }
 
+// The one-step model of the tyre fit as a rollout model: tf_row<false> with the set's tyre constants, prepared
+// once per wave.  A rollout model supplies step(x, controls and truth of the step, o) and wrap_yaw: whether the
+// yaw error is the wrapped difference.  (The plant's is RoPlantModel of mr_plantroll.h.)
 template <int KIND>
-MR_WV_FN void ro_chunk(const RoArgs& A, int p, int pl, int chunk, double* lds, const Wv& w) {
-  const mr_tyrefit_config& V = A.cfg;
-  constexpr int np = KIND == MR_TYRE_PACEJKA ? 18 : 2;
-  const TfTyres T = tf_tyres(KIND, A.params + (int64_t)p * np, A.Fz + 2 * (int64_t)p);
+struct RoTyreModel {
+  static constexpr bool wrap_yaw = false;  // the log's yaw and the model's are both continuous
+  const mr_tyrefit_config& V;
+  const TfTyres T;
+  MR_HD RoTyreModel(const mr_tyrefit_config& cfg, const RoArgs& A, int p)
+      : V(cfg),
+        T(tf_tyres(KIND, A.params + (int64_t)p * (KIND == MR_TYRE_PACEJKA ? 18 : 2), A.per_set + 2 * (int64_t)p)) {}
+  MR_HD void step(const double* x, const RoStep& s, double* o) const {
+    double row[TF_COLS];
+    for (int c = 0; c < 6; ++c) row[c] = x[c];
+    row[6] = s.thr;
+    row[7] = s.steer;
+    row[8] = s.ts;
+    for (int c = 0; c < 6; ++c) row[9 + c] = s.truth[c];
+    tf_row<false>(V, T, row, o, nullptr);
+  }
+};
+
+// The wave body of every rollout: set p of the call, whose partials are set pl of the buffer (the sets of one
+// launch), chunk `chunk` of its starts (lds: RO_LDS_WORDS doubles shared by the wave).
+template <class Model>
+MR_WV_FN void ro_chunk(const RoArgs& A, const Model& M, int p, int pl, int chunk, double* lds, const Wv& w) {
   const int i = chunk * WL + w.lane;
   const bool active = i < A.n_start;
   const int s = A.start[active ? i : 0];  // idle lanes of a partial chunk follow a valid start and never count
-  double row[TF_COLS], o[6];
+  double x[6], o[6];
   bool alive = active;
   for (int c = 0; c < 6; ++c) {
-    row[c] = A.log[(int64_t)c * A.T + s];
-    alive = alive && tf_finite(row[c]);
+    x[c] = A.log[(int64_t)c * A.T + s];
+    alive = alive && tf_finite(x[c]);
   }
   // step k + 1's controls and truth are loaded while step k computes
   RoStep cur, nxt;
@@ -111,11 +147,7 @@ MR_WV_FN void ro_chunk(const RoArgs& A, int p, int pl, int chunk, double* lds, c
   double* part = A.partials + ((int64_t)pl * A.n_chunk + chunk) * A.H * RO_NPART;
   for (int k = 1; k <= A.H; ++k) {
     if (k < A.H) ro_load(A.log, A.T, s, k + 1, &nxt);
-    row[6] = cur.thr;
-    row[7] = cur.steer;
-    row[8] = cur.ts;
-    for (int c = 0; c < 6; ++c) row[9 + c] = cur.truth[c];
-    tf_row<false>(V, T, row, o, nullptr);
+    M.step(x, cur, o);
     for (int c = 0; c < 6; ++c) alive = alive && tf_finite(o[c]);
     if (A.pred && active)
       for (int c = 0; c < 6; ++c)
@@ -123,7 +155,8 @@ MR_WV_FN void ro_chunk(const RoArgs& A, int p, int pl, int chunk, double* lds, c
 #if MR_ROLLOUT_STATS
     double v[RO_NPART];
     for (int c = 0; c < 6; ++c) {
-      const double e = cur.truth[c] - o[c];
+      double e = cur.truth[c] - o[c];
+      if (Model::wrap_yaw && c == 2) e = atan2(sin(e), cos(e));
       v[4 * c + 0] = alive ? e : 0.0;
       v[4 * c + 1] = alive ? e * e : 0.0;
       v[4 * c + 2] = alive ? -e : -INFINITY;  // min e = -max(-e)
@@ -138,15 +171,14 @@ MR_WV_FN void ro_chunk(const RoArgs& A, int p, int pl, int chunk, double* lds, c
     if (w.lane == 0)
       for (int j = 0; j < RO_NPART; ++j) part[(int64_t)(k - 1) * RO_NPART + j] = 0.0;
 #endif
-    for (int c = 0; c < 6; ++c) row[c] = alive ? o[c] : row[c];  // a stopped lane keeps its last finite state
+    for (int c = 0; c < 6; ++c) x[c] = alive ? o[c] : x[c];  // a stopped lane keeps its last finite state
     if (k < A.H) cur = nxt;
   }
 }
-// set p of the call, whose partials are set pl of the buffer (the sets of one launch)
-// (lds: RO_LDS_WORDS doubles shared by the wave)
-MR_WV_FN void ro_chunk_kind(const RoArgs& A, int p, int pl, int chunk, double* lds, const Wv& w) {
-  if (A.cfg.kind == MR_TYRE_PACEJKA) ro_chunk<MR_TYRE_PACEJKA>(A, p, pl, chunk, lds, w);
-  else ro_chunk<MR_TYRE_LINEAR>(A, p, pl, chunk, lds, w);
+MR_WV_FN void ro_chunk_kind(const mr_tyrefit_config& cfg, const RoArgs& A, int p, int pl, int chunk, double* lds,
+                            const Wv& w) {
+  if (cfg.kind == MR_TYRE_PACEJKA) ro_chunk(A, RoTyreModel<MR_TYRE_PACEJKA>(cfg, A, p), p, pl, chunk, lds, w);
+  else ro_chunk(A, RoTyreModel<MR_TYRE_LINEAR>(cfg, A, p), p, pl, chunk, lds, w);
 }
 
 // partials of set p (local index in the partials buffer: pl) at step k added in chunk order

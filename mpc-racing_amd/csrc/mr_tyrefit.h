@@ -416,6 +416,14 @@ struct TfFitArgs {
   int32_t* flag;        // [R]
   double* p_steps;      // optional [R][epochs * ceil(n_train / 64)][n_par]: parameters after every step
 };
+inline TfFitArgs make_tf_fit_args(const mr_tyrefit_config& cfg, int n_train, const double* train, int n_val,
+                                  const double* val, int R, const double* init, const double* Fz,
+                                  const double* hyper, const int32_t* perm, int64_t perm_stride_run, double* p_final,
+                                  double* p_best, double* train_loss, double* val_loss, double* lr_hist,
+                                  int32_t* flag, double* p_steps) {
+  return TfFitArgs{cfg,  n_train,         n_val,   R,      train,      val,      init,    Fz,   hyper,
+                   perm, perm_stride_run, p_final, p_best, train_loss, val_loss, lr_hist, flag, p_steps};
+}
 
 MR_HD void tf_load_row(const double* rows, int n, int i, double* row) {
   for (int c = 0; c < TF_COLS; ++c) row[c] = rows[(int64_t)c * n + i];

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <cmath>
+#include <type_traits>
 #endif
 
 // Address-space qualifiers: keep the workspace in the global and the exchange buffers in the
@@ -460,6 +461,22 @@ inline void host_wave_run(HostWave& hw, void (*body)(HostWave*, int, void*), voi
   }
   free(hw.stacks);
   hw.stacks = nullptr;
+}
+
+// f(const Wv&) as one emulated wavefront: allocate it, run the 64 fibers, a final rendezvous (every lane done
+// before the wave is torn down), free it.
+template <class F>
+inline void host_wave_call(F&& f) {
+  HostWave* hw = new HostWave();
+  host_wave_run(
+      *hw,
+      [](HostWave* h, int lane, void* arg) {
+        Wv w{lane, h};
+        (*(typename std::remove_reference<F>::type*)arg)(w);
+        wsync(w);
+      },
+      (void*)&f);
+  delete hw;
 }
 
 template <typename T>

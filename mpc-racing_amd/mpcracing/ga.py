@@ -140,12 +140,9 @@ def breed_launch(be, host_twin, dims, genes, ld, col, times, avg, bounds, consts
     lo = be.ptr(bounds[0]) if bounds is not None else None
     hi = be.ptr(bounds[1]) if bounds is not None else None
     p = lambda a: None if a is None else be.ptr(a)  # noqa: E731
-    args = [n_island, P, K, D, pairs, p(genes), ld, col, p(times), p(avg), lo, hi, *[float(c) for c in consts],
-            int(seed), int(island0), int(generation), p(r), p(best_r), p(best_idx), p(best_genes)]
-    if host_twin:
-        be.check(be.lib.mrh_ga_breed(*args))
-    else:
-        be.check(be.lib.mr_ga_breed(*args, be.stream()))
+    be.call("ga_breed", n_island, P, K, D, pairs, p(genes), ld, col, p(times), p(avg), lo, hi,
+            *[float(c) for c in consts], int(seed), int(island0), int(generation), p(r), p(best_r), p(best_idx),
+            p(best_genes), sync=False)
 
 
 def breed(genes, times, avg, pairs=1, lo=None, hi=None, kT=KT, lambda_T=LAMBDA_T, mutation_rate=MUTATION_RATE, seed=0,

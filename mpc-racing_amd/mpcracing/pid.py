@@ -121,12 +121,7 @@ def control(track, state, mem, gains, dt, host_twin=False, device=0):
     be = _backend(tr, host_twin)
     d = [be.put(state), be.put(mem), be.put(g)]
     out = be.empty((abi.MR_PID_NOUT, n))
-    args = [n, be.ptr(d[0]), be.ptr(d[1]), g.shape[0], be.ptr(d[2]), float(dt), be.ptr(out)]
-    if host_twin:
-        be.check(be.lib.mrh_pid_control(*tr.args(), *args))
-    else:
-        be.check(be.lib.mr_pid_control(tr.h, *args, be.stream()))
-        be.torch.cuda.synchronize(be.dev)
+    be.call("pid_control", n, be.ptr(d[0]), be.ptr(d[1]), g.shape[0], be.ptr(d[2]), float(dt), be.ptr(out), track=tr)
     return be.get(out), np.array(be.get(d[1]))
 
 
@@ -213,13 +208,8 @@ def drive(track, state0, ticks, gains=None, model="blend", params=None, dt=0.05,
         Tc = min(T_MAX, T - t0)
         log = be.empty((len(kept), Tc, n)) if kept else None
         td = be.empty((n,), np.int32)
-        args = [model_id, n, Tc, float(dt), be.ptr(d_state), be.ptr(d_mem), g.shape[0], be.ptr(d_g), q.shape[0],
-                be.ptr(d_q), mask, be.ptr(log) if kept else None, be.ptr(td)]
-        if host_twin:
-            be.check(be.lib.mrh_pid_drive(*tr.args(), *args, 16))
-        else:
-            be.check(be.lib.mr_pid_drive(tr.h, *args, be.stream()))
-            be.torch.cuda.synchronize(be.dev)
+        be.call("pid_drive", model_id, n, Tc, float(dt), be.ptr(d_state), be.ptr(d_mem), g.shape[0], be.ptr(d_g),
+                q.shape[0], be.ptr(d_q), mask, be.ptr(log) if kept else None, be.ptr(td), track=tr)
         td = be.get(td)
         done += np.where(done == t0, td, 0)  # a stopped vehicle stays stopped in the later calls
         chunks.append(be.get(log) if kept else None)
@@ -240,13 +230,7 @@ def evaluate_gains(track, population, bounds, ticks, v0=15.0, model="blend", par
     reached).  Returns (times, the PidResult)."""
     from .closed_loop import ClosedLoop
     from .ga import crossing_times
-    pop = np.atleast_2d(np.asarray(population, np.float64))
-    if pop.shape[1] == 4:
-        full = np.tile(gains(), (pop.shape[0], 1))
-        full[:, 2:6] = pop
-        pop = full
-    elif pop.shape[1] != abi.MR_PID_NGAIN:
-        raise ValueError(f"population: expected [P][4] or [P][{abi.MR_PID_NGAIN}], got {pop.shape}")
+    pop = _full_gains(population)
     P, K = pop.shape[0], len(bounds) - 1
     starts = np.asarray(bounds[:-1], np.float64)
     ends = np.asarray(bounds[1:], np.float64)
@@ -296,12 +280,9 @@ class _SegmentDrive:
     def launch(self, d_gains, ticks, d_times, d_done):
         be = self.be
         p = lambda a: None if a is None else be.ptr(a)  # noqa: E731
-        args = [self.model_id, self.n, self.K, int(ticks), self.dt, p(self.start), p(self.s_start), p(self.s_end),
-                p(d_gains), self.P, p(self.q), p(d_times), p(d_done)]
-        if self.host_twin:
-            be.check(be.lib.mrh_pid_segment_times(*self.tr.args(), *args, 16))
-        else:
-            be.check(be.lib.mr_pid_segment_times(self.tr.h, *args, be.stream()))
+        be.call("pid_segment_times", self.model_id, self.n, self.K, int(ticks), self.dt, p(self.start),
+                p(self.s_start), p(self.s_end), p(d_gains), self.P, p(self.q), p(d_times), p(d_done), track=self.tr,
+                sync=False)
 
     def sync(self):
         if not self.host_twin:

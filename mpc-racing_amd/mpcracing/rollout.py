@@ -104,55 +104,63 @@ class RolloutErrors:
         return cost
 
 
+def _log(log):
+    log = np.ascontiguousarray(log, np.float64)
+    if log.ndim != 2 or log.shape[0] != 9:
+        raise ValueError(f"log: expected [9][T], got {log.shape}")
+    return log
+
+
+def _rollout(name, lead, log, params, per_set, horizon, starts, keep_pred, device, host_twin):
+    """What both rollouts share: the horizon and the starts, the buffers, the ``mr_<name>`` call and its result.
+    lead: the entry's first argument (tyre config / plant model); per_set: the array that follows the parameters
+    (Fz [P][2] / dt [P] or None)."""
+    T, H, P = log.shape[1], int(horizon), params.shape[0]
+    if H < 1 or H > T - 1:
+        raise ValueError(f"horizon {H} outside [1, T - 1 = {T - 1}]")
+    starts = np.arange(T - H, dtype=np.int32) if starts is None else np.ascontiguousarray(starts, np.int32).ravel()
+    n = len(starts)
+    be = _Host() if host_twin else _Device(device)
+    d = [be.put(log), be.put(starts), be.put(params)] + ([be.put(per_set)] if per_set is not None else [])
+    stats, count = be.empty((P, H, 6, 4)), be.empty((P, H), np.int32)
+    pred = be.empty((P, H, 6, n)) if keep_pred else None
+    be.call(name, lead, T, be.ptr(d[0]), n, be.ptr(d[1]), H, P, be.ptr(d[2]),
+            be.ptr(d[3]) if per_set is not None else None, be.ptr(stats), be.ptr(count),
+            be.ptr(pred) if keep_pred else None)
+    return RolloutErrors(be.get(stats), be.get(count), be.get(pred) if keep_pred else None, starts, H)
+
+
+def _step(name, lead, state, cmd, dt, params, per_set, device, host_twin):
+    """One ``mr_<name>`` step of n vehicles (``vehicle_step``, ``plant_step``); lead and per_set as in ``_rollout``."""
+    state = np.ascontiguousarray(state, np.float64).reshape(6, -1)
+    n = state.shape[1]
+    cmd = np.ascontiguousarray(cmd, np.float64).reshape(2, n)
+    be = _Host() if host_twin else _Device(device)
+    d = [be.put(state), be.put(cmd), be.put(params)] + ([be.put(per_set)] if per_set is not None else [])
+    out = be.empty((6, n))
+    be.call(name, lead, n, be.ptr(d[0]), be.ptr(d[1]), float(dt), params.shape[0], *[be.ptr(a) for a in d[2:]],
+            be.ptr(out))
+    return be.get(out)
+
+
 def rollout_errors(log, tyres, kind=None, horizon=10, starts=None, keep_pred=False, device=0, host_twin=False,
                    **vehicle):
     """Roll the one-step model with ``tyres`` forward ``horizon`` steps from every start row of ``log`` [9][T]
     (``load_log``) and reduce truth minus prediction.  tyres: a ``FitResult`` (all its runs) or (params
     [P][n_par], Fz [P][2] or None) with ``kind``; starts: row indices in [0, T - 1 - horizon] (default: all of
     them).  Returns a RolloutErrors."""
-    log = np.ascontiguousarray(log, np.float64)
-    if log.ndim != 2 or log.shape[0] != 9:
-        raise ValueError(f"log: expected [9][T], got {log.shape}")
+    log = _log(log)
     kind, params, Fz = _tyres(tyres, kind)
-    T, H, P = log.shape[1], int(horizon), params.shape[0]
-    if H < 1 or H > T - 1:
-        raise ValueError(f"horizon {H} outside [1, T - 1 = {T - 1}]")
-    starts = np.arange(T - H, dtype=np.int32) if starts is None else np.ascontiguousarray(starts, np.int32).ravel()
-    n = len(starts)
     cfg = make_config(kind, host_twin=host_twin, **vehicle)
-    be = _Host() if host_twin else _Device(device)
-    d = [be.put(log), be.put(starts), be.put(params), be.put(Fz)]
-    stats, count = be.empty((P, H, 6, 4)), be.empty((P, H), np.int32)
-    pred = be.empty((P, H, 6, n)) if keep_pred else None
-    args = [ctypes.byref(cfg), T, be.ptr(d[0]), n, be.ptr(d[1]), H, P, be.ptr(d[2]), be.ptr(d[3]), be.ptr(stats),
-            be.ptr(count), be.ptr(pred) if keep_pred else None]
-    if host_twin:
-        be.check(be.lib.mrh_tyre_rollout(*args, 16))
-    else:
-        be.check(be.lib.mr_tyre_rollout(*args, be.stream()))
-        be.torch.cuda.synchronize(be.dev)
-    return RolloutErrors(be.get(stats), be.get(count), be.get(pred) if keep_pred else None, starts, H)
+    return _rollout("tyre_rollout", ctypes.byref(cfg), log, params, Fz, horizon, starts, keep_pred, device, host_twin)
 
 
 def vehicle_step(state, cmd, dt, tyres, kind=None, device=0, host_twin=False, **vehicle):
     """One model step of n vehicles: state [6][n], cmd [2][n] = (throttle - brake, steer) -> [6][n] (numpy).
     tyres as in ``rollout_errors``: one set shared by all vehicles, or one per vehicle."""
-    state = np.ascontiguousarray(state, np.float64).reshape(6, -1)
-    n = state.shape[1]
-    cmd = np.ascontiguousarray(cmd, np.float64).reshape(2, n)
     kind, params, Fz = _tyres(tyres, kind)
     cfg = make_config(kind, host_twin=host_twin, **vehicle)
-    be = _Host() if host_twin else _Device(device)
-    d = [be.put(state), be.put(cmd), be.put(params), be.put(Fz)]
-    out = be.empty((6, n))
-    args = [ctypes.byref(cfg), n, be.ptr(d[0]), be.ptr(d[1]), float(dt), params.shape[0], be.ptr(d[2]), be.ptr(d[3]),
-            be.ptr(out)]
-    if host_twin:
-        be.check(be.lib.mrh_vehicle_step(*args))
-    else:
-        be.check(be.lib.mr_vehicle_step(*args, be.stream()))
-        be.torch.cuda.synchronize(be.dev)
-    return be.get(out)
+    return _step("vehicle_step", ctypes.byref(cfg), state, cmd, dt, params, Fz, device, host_twin)
 
 
 # ---- the models/ plant with run-time parameters (csrc/mr_plant.h, mr_plantroll.h) ----
@@ -195,45 +203,15 @@ def plant_rollout_errors(log, model, params=None, dt=None, horizon=10, starts=No
     default: one default set) forward ``horizon`` steps from every start row of ``log`` [9][T] and reduce truth
     minus prediction (the yaw error wrapped to (-pi, pi]).  The step length is the log's ``ts`` or, with ``dt``
     (a number or [P]), one fixed step per set.  One ``mr_plant_rollout`` call; returns a RolloutErrors."""
-    log = np.ascontiguousarray(log, np.float64)
-    if log.ndim != 2 or log.shape[0] != 9:
-        raise ValueError(f"log: expected [9][T], got {log.shape}")
+    log = _log(log)
     model, params = _plant_args(model, params)
-    T, H, P = log.shape[1], int(horizon), params.shape[0]
-    if H < 1 or H > T - 1:
-        raise ValueError(f"horizon {H} outside [1, T - 1 = {T - 1}]")
-    starts = np.arange(T - H, dtype=np.int32) if starts is None else np.ascontiguousarray(starts, np.int32).ravel()
-    n = len(starts)
     if dt is not None:
-        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (P,)))
-    be = _Host() if host_twin else _Device(device)
-    d = [be.put(log), be.put(starts), be.put(params)] + ([be.put(dt)] if dt is not None else [])
-    stats, count = be.empty((P, H, 6, 4)), be.empty((P, H), np.int32)
-    pred = be.empty((P, H, 6, n)) if keep_pred else None
-    args = [model, T, be.ptr(d[0]), n, be.ptr(d[1]), H, P, be.ptr(d[2]), be.ptr(d[3]) if dt is not None else None,
-            be.ptr(stats), be.ptr(count), be.ptr(pred) if keep_pred else None]
-    if host_twin:
-        be.check(be.lib.mrh_plant_rollout(*args, 16))
-    else:
-        be.check(be.lib.mr_plant_rollout(*args, be.stream()))
-        be.torch.cuda.synchronize(be.dev)
-    return RolloutErrors(be.get(stats), be.get(count), be.get(pred) if keep_pred else None, starts, H)
+        dt = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float64), (params.shape[0],)))
+    return _rollout("plant_rollout", model, log, params, dt, horizon, starts, keep_pred, device, host_twin)
 
 
 def plant_step(state, cmd, dt, model, params=None, device=0, host_twin=False):
     """One plant step of n vehicles: state [6][n], cmd [2][n] = (throttle - brake, steer) -> [6][n] (numpy).
     params: one vector shared by all vehicles (default: the defaults) or one per vehicle ([n][MR_PLANT_NPAR])."""
-    state = np.ascontiguousarray(state, np.float64).reshape(6, -1)
-    n = state.shape[1]
-    cmd = np.ascontiguousarray(cmd, np.float64).reshape(2, n)
     model, params = _plant_args(model, params)
-    be = _Host() if host_twin else _Device(device)
-    d = [be.put(state), be.put(cmd), be.put(params)]
-    out = be.empty((6, n))
-    args = [model, n, be.ptr(d[0]), be.ptr(d[1]), float(dt), params.shape[0], be.ptr(d[2]), be.ptr(out)]
-    if host_twin:
-        be.check(be.lib.mrh_plant_step_params(*args))
-    else:
-        be.check(be.lib.mr_plant_step_params(*args, be.stream()))
-        be.torch.cuda.synchronize(be.dev)
-    return be.get(out)
+    return _step("plant_step_params", model, state, cmd, dt, params, None, device, host_twin)

@@ -101,6 +101,14 @@ class _Device:
         if rc != 0:
             raise RuntimeError(f"libmpcracing error {rc}: {self.lib.mr_last_error().decode()}")
 
+    def call(self, name, *args, track=None, sync=True):
+        """``mr_<name>(*args)`` on the current stream, its return code checked, then (``sync``) a synchronise of the
+        device; ``track``: the DeviceTrack whose handle leads the arguments."""
+        lead = [] if track is None else [track.h]
+        self.check(getattr(self.lib, "mr_" + name)(*lead, *args, self.stream()))
+        if sync:
+            self.torch.cuda.synchronize(self.dev)
+
 
 class _Host:
     """TEST-ONLY: numpy arrays and the host build of the same source."""
@@ -125,6 +133,15 @@ class _Host:
         if rc != 0:
             raise RuntimeError(f"host twin error {rc}: {self.lib.mrh_tyrefit_last_error().decode()}")
 
+    # the entries that spread their waves or vehicles over OpenMP threads: they take a thread count last
+    THREADED = {"tyre_fit", "tyre_rollout", "plant_rollout", "pid_drive", "pid_segment_times"}
+
+    def call(self, name, *args, track=None, sync=True):
+        """``mrh_<name>(*args)`` (with 16 threads where the entry is ``THREADED``), its return code checked;
+        ``track``: the host track whose blob arguments lead."""
+        lead = [] if track is None else track.args()
+        self.check(getattr(self.lib, "mrh_" + name)(*lead, *args, *([16] if name in self.THREADED else [])))
+
 
 def loss_grad(rows, params, Fz=None, kind="pacejka", device=0, host_twin=False, **vehicle):
     """Loss (nn.MSELoss: mean over rows x 6) and its gradient for P parameter sets over rows [n][15].
@@ -141,12 +158,8 @@ def loss_grad(rows, params, Fz=None, kind="pacejka", device=0, host_twin=False, 
     d_rows, d_par, d_Fz = be.put(rows.T), be.put(params), be.put(Fz)
     loss, grad = be.empty((P,)), be.empty((P, npar))
     n = rows.shape[0]
-    if host_twin:
-        be.check(be.lib.mrh_tyre_loss_grad(ctypes.byref(cfg), n, be.ptr(d_rows), P, be.ptr(d_par), be.ptr(d_Fz),
-                                           be.ptr(loss), be.ptr(grad)))
-    else:
-        be.check(be.lib.mr_tyre_loss_grad(ctypes.byref(cfg), n, be.ptr(d_rows), P, be.ptr(d_par), be.ptr(d_Fz),
-                                          be.ptr(loss), be.ptr(grad), be.stream()))
+    be.call("tyre_loss_grad", ctypes.byref(cfg), n, be.ptr(d_rows), P, be.ptr(d_par), be.ptr(d_Fz), be.ptr(loss),
+            be.ptr(grad), sync=False)  # the entry itself ends in a stream synchronise
     return be.get(loss), be.get(grad)
 
 
@@ -261,11 +274,7 @@ def fit_tyres(train, val, kind="pacejka", inits=None, Fz=None, runs=1, seeds=Non
     steps = be.empty((R, int(epochs) * ((n + 63) // 64), npar)) if record_steps else None
     args = [ctypes.byref(cfg), n, be.ptr(d[0]), val.shape[0], be.ptr(d[1]), R, be.ptr(d[2]), be.ptr(d[3]),
             be.ptr(d[4]), be.ptr(d[5]), stride] + [be.ptr(o) for o in out] + [be.ptr(steps) if record_steps else None]
-    if host_twin:
-        be.check(be.lib.mrh_tyre_fit(*args, 16))
-    else:
-        be.check(be.lib.mr_tyre_fit(*args, be.stream()))
-        be.torch.cuda.synchronize(be.dev)
+    be.call("tyre_fit", *args)
     p_final, p_best, tl, vl, lrh, flag = [be.get(o) for o in out]
     res = FitResult(kind, Fz, p_final, p_best, tl, vl, lrh, flag, seeds)
     res.steps = be.get(steps) if record_steps else None
