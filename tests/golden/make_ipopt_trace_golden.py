@@ -180,26 +180,45 @@ def host_trace(case, scalar, precision="fp64"):
                     trace_cap=TRACE_CAP, duals=not scalar)
 
 
-def _n_cmp(case, log):
-    """(n_cmp, worst deviations over those rows) from both host fp64 builds."""
+def n_cmp_rule(log, traces, label=""):
+    """(n_cmp, worst deviations over those rows) of the oracle's ``log`` from the host fp64 builds' ``traces``
+    (scalar, wave): the longest prefix of non-restoration rows within N_CMP_RTOL in alpha, theta and kkt; mu and
+    delta asserted within 1e-12 on it.  Shared with make_config_grid_golden.py."""
     n = len(log)
     ok = log[:, LOG_COL["in_resto"]] == 0.0
     worst = {}
     devs = {}
-    for scalar in (True, False):
-        tr = host_trace(case, scalar)["trace"][:n]
+    for which, tr in enumerate(traces):
+        tr = tr[:n]
         ok &= tr[:, TRACE_COL["marker"]] > -200.0  # the product's own restoration rows
         for col in ("alpha", "theta", "kkt", "mu", "delta"):
             d = rel_dev(tr[:, TRACE_COL[col]], log[:, LOG_COL[col]], THETA_ATOL if col == "theta" else 0.0)
-            devs[col, scalar] = d
+            devs[col, which] = d
             if col in ("alpha", "theta", "kkt"):
                 ok &= d <= N_CMP_RTOL
     bad = np.nonzero(~ok)[0]
     n_cmp = int(bad[0]) if bad.size else n
-    for (col, scalar), d in devs.items():
+    for (col, _which), d in devs.items():
         worst[col] = max(worst.get(col, 0.0), float(d[:n_cmp].max(initial=0.0)))
-    assert worst["mu"] <= 1e-12 and worst["delta"] <= 1e-12, (case, worst)
+    assert worst["mu"] <= 1e-12 and worst["delta"] <= 1e-12, (label, worst)
     return n_cmp, worst
+
+
+def fp32_recipe(log, t64, t32, label=""):
+    """(marker, fp32_dev) of an fp32 case from the host wave build's fp64 and fp32 traces: the fp64 build's
+    markers on the oracle's rows, asserted equal in the fp32 build, and the fp32 build's worst relative deviation
+    from the oracle per column of FP32_COLS.  Shared with make_config_grid_golden.py."""
+    m64 = t64[:K_FP32, TRACE_COL["marker"]]
+    t32 = t32[:K_FP32]
+    assert np.array_equal(t32[:, TRACE_COL["marker"]], m64), (label, t32[:, TRACE_COL["marker"]], m64)
+    dev = np.array([rel_dev(t32[:, TRACE_COL[c]], log[:, LOG_COL[c]]).max() for c in FP32_COLS])
+    assert np.isfinite(dev).all(), (label, dev)  # delta's zero rows are zero in fp32 too
+    return m64, dev
+
+
+def _n_cmp(case, log):
+    """(n_cmp, worst deviations over those rows) from both host fp64 builds."""
+    return n_cmp_rule(log, [host_trace(case, scalar)["trace"] for scalar in (True, False)], case)
 
 
 def main():
@@ -230,11 +249,8 @@ def assemble(res):
                      max_delta=float(log[:, LOG_COL["delta"]].max()), host_worst_dev=worst)
         if kind == "fp32":
             assert n_cmp == K_FP32 == len(log), (case, n_cmp, len(log))
-            m64 = host_trace(case, False)["trace"][:K_FP32, TRACE_COL["marker"]]
-            t32 = host_trace(case, False, "fp32")["trace"][:K_FP32]
-            assert np.array_equal(t32[:, TRACE_COL["marker"]], m64), (case, t32[:, TRACE_COL["marker"]], m64)
-            dev = np.array([rel_dev(t32[:, TRACE_COL[c]], log[:, LOG_COL[c]]).max() for c in FP32_COLS])
-            assert np.isfinite(dev).all(), (case, dev)  # delta's zero rows are zero in fp32 too
+            m64, dev = fp32_recipe(log, host_trace(case, False)["trace"], host_trace(case, False, "fp32")["trace"],
+                                   case)
             arrays[f"{case}/marker"] = m64
             arrays[f"{case}/fp32_dev"] = dev
             entry["host_fp32_dev"] = dict(zip(FP32_COLS, dev.tolist()))

@@ -49,10 +49,11 @@ def cases(*kinds):
     return [c for c, (_n, _i, kind) in GEN.CASES.items() if kind in kinds]
 
 
-def check_rows(case, trace, label):
+def check_rows(case, trace, label, fx=None):
     """The first n_cmp rows of ``trace`` [rows][8] (mr_outputs.trace) against the oracle's log, at the bars
-    above.  Returns the worst relative deviation per column (theta: after its absolute allowance)."""
-    arrays, index = fixture()
+    above.  Returns the worst relative deviation per column (theta: after its absolute allowance).  ``fx``: another
+    fixture of the same layout as (arrays, index) -- tests/config_grid_cases.py -- instead of this module's."""
+    arrays, index = fx or fixture()
     log, n = arrays[f"{case}/log"], index[case]["n_cmp"]
     assert n >= 1 and not log[:n, LOG_COL["in_resto"]].any()
     assert (trace[:n, TRACE_COL["marker"]] > -200.0).all(), f"{label} {case}: restoration rows within n_cmp"
@@ -69,9 +70,9 @@ def check_rows(case, trace, label):
     return worst
 
 
-def check_whole(case, status, iters, obj, label):
+def check_whole(case, status, iters, obj, label, fx=None):
     """A whole-solve case compared to its last row: the same termination iteration, status and objective."""
-    _arrays, index = fixture()
+    _arrays, index = fx or fixture()
     e = index[case]
     if not e["whole"]:
         return
@@ -80,9 +81,9 @@ def check_whole(case, status, iters, obj, label):
     np.testing.assert_allclose(obj, e["obj"], rtol=1e-10, err_msg=f"{label} {case}: objective")
 
 
-def check_lam_g(case, mine, label):
+def check_lam_g(case, mine, label, fx=None):
     """tests/test_duals.py::_check: every present row within 1e-7 of max |lam_g|; absent rows are NaN."""
-    arrays, _index = fixture()
+    arrays, _index = fx or fixture()
     lg = arrays[f"{case}/lam_g"]
     ok = ~np.isnan(mine)
     assert ok.sum() == len(lg), f"{label} {case}: {int(ok.sum())} rows present, {len(lg)} expected"

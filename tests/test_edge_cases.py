@@ -63,7 +63,11 @@ def test_empty_batch():
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", [1, 2, 63])
 def test_horizon_extremes_match_host_build(N):
-    """Same solver source on the GPU and on the host at the smallest horizons and at N = 63."""
+    """Same solver source on the GPU and on the host at the smallest horizons and at N = 63.
+
+    An error the two builds share passes here (final point, one source).  tests/test_gpu_config_grid.py holds the
+    gfx950 build -- and tests/test_config_grid.py both host builds -- to the dense IPOPT oracle's iteration log at
+    N = 1, 2, 3, 15 .. 17, 31 .. 33, 47 .. 49, 62, 63 and over the models, lane rows and parameters."""
     pytest.importorskip("torch")
     import host_twin as ht
     from mpcracing.batch import BatchSolver
