@@ -1041,11 +1041,13 @@ struct WaveSolver {
   // frag_load issues the 8 gathers unconditionally two stages ahead, frag_finish applies the
   // selects when the stage is factorised, so no load is sunk into a lane-divergent branch.
   static constexpr int NGATHER = 12;
+  static constexpr bool P_SYM = sizeof(T) == 8;  // the LDS tile of P^ kept symmetric (frag_plan)
   struct FragPlan {
     int off[NGATHER];  // record offsets: data entries, or the record's constant slots (CONE, CZERO, SELP, SEL0);
                        // 8..11: the slack shift's entry of each D register (delta_s: HD, or GD in column 14)
     unsigned dlt;  // D registers on the diagonal of H (+ delta)
     int st_p[4], lp[4];  // per D register: record / LDS targets (discard slots if none)
+    int lpm[4];          // per D register: the LDS target of the mirrored entry (an entry above P's diagonal)
   };
   // record slot of entry (i, j) of E^ (either stage class k = 0 / k > 0): its data word, or the
   // constant slot holding its value; CZERO when !keep
@@ -1081,13 +1083,21 @@ struct WaveSolver {
         const int hs = (a < NZ && c < NZ) ? hd_slot(lo_, hi_) : -1;
         fp.off[8 + v] = hs >= 0 ? RCF::HD + hs : ((a < NZ && c == 14) ? RCF::GD + a_ : RCF::CZERO);
       }
-      // outputs of D register v: packed-upper P | p (column 14) to the record; the whole tile of P^
-      // (both triangles as the product computes them, one LDS write per register) to LDS
+      // outputs of D register v: packed-upper P | p (column 14) to the record and to the LDS tile of P^.
+      // The tile's lower triangle is the mirror of the upper one (a second LDS write of the lanes above the
+      // diagonal), not the entries the product computes there: Q_xx - W^T W rounds (i, j) and (j, i)
+      // differently, and the recursion does not damp the antisymmetric part of P^ -- with W from Q_ux alone
+      // it propagates by A^T S A - A^T S B K + K^T B^T S A, not by the closed loop's (A + B K)^T S (A + B K),
+      // so where the open-loop map is large (a dynamics row of a car braking to a few m/s: entries of 100 and
+      // more) it grew 20-fold per stage and cost the step 6 digits (tests/test_shift.py).  The record's P
+      // always was the upper triangle; the scalar solver keeps no other.  fp64 only (P_SYM): the fp32 solve
+      // keeps both triangles as the product computes them.
       const int junk_r = RCF::JUNK, junk_l = LJUNK_OFF - LP_OFF + lane;  // lp index from LP
       const bool ax = a < NX, sq = ax & (c < NX), up = sq & (a <= c);
       const bool c14 = ax & (c == 14);
       fp.st_p[v] = up ? RCF::P + pidx(a, c) : (c14 ? RCF::PV0 + a : junk_r);
-      fp.lp[v] = sq ? a * LDS_LD + c : (c14 ? a * LDS_LD + 11 : junk_l);
+      fp.lp[v] = (P_SYM ? up : sq) ? a * LDS_LD + c : (c14 ? a * LDS_LD + 11 : junk_l);
+      fp.lpm[v] = (P_SYM & sq & (a < c)) ? c * LDS_LD + a : junk_l;
     }
   }
   // DS: the slack shift's gathers (8..11) only when delta > 0 (a delta = 0 factorisation skips them)
@@ -1290,6 +1300,7 @@ struct WaveSolver {
         const T pv = dq[v] - dw[v];
         rb.st(pv, Rk, (unsigned)fp.st_p[v]);
         LP[fp.lp[v]] = pv;
+        if constexpr (P_SYM) LP[fp.lpm[v]] = pv;  // P^ symmetric: (j, i) = (i, j) of the upper triangle (frag_plan)
       }
       wsync_lds(w);
       return piv_ok & noise_ok;

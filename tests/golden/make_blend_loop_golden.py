@@ -2,6 +2,8 @@
 vehicles, as computed on an MI355X by the library of the commit BEFORE the learned plant was added
 (``--package-root`` names that commit's ``mpc-racing_amd``).  tests/test_gpu_rollout.py holds the same setup
 (``run_blend`` below) bitwise equal to the recording: adding ``plant="learned"`` changed no other plant path.
+Recorded again when the fp64 Riccati sweep's cost-to-go tile was made symmetric (mr_wave.h frag_plan):
+the loop's fp64 MPC solves (tol 1e-10) moved in their last bits on purpose, nothing of the plant did.
 
 TEST FIXTURE GENERATOR (needs the GPU; run once per change of the setup).
 

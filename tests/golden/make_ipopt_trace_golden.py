@@ -19,7 +19,9 @@ is compared is one on which the two linear algebras (dense LDL there, Riccati he
 by rounding.  mu and delta must be within 1e-12 on those rows.  Asserted, not measured (MIN_N_CMP): n_cmp is the
 whole solve for C2_1, C2_8, C4_0 and C5_0, at least 14 for the prefix cases and at least 30 for both C1dyn cases.
 A case whose solve converged and is compared to its last iteration is marked ``whole`` in the index; the tests
-then also compare its iteration count, status and objective.
+then also compare its iteration count, status and objective.  Requiring both builds means that the rule cannot see a
+loss of accuracy that only the wave build has: it shortens n_cmp or drops the case and fails nothing.
+make_shift_golden.py covers that: its rows are selected by the scalar build alone.
 
 Cases
   prefix, 14 iterations (tol 1e-8, acceptable 1e-6 over 15):  C2_5 and C2_6 (kinematic), C3_374 and C3_0
@@ -143,41 +145,57 @@ def rel_dev(mine, ref, atol=0.0):
         return np.where(d == 0.0, 0.0, d / np.abs(ref))
 
 
-def _oracle(case):
+def oracle_solve(cfg, sub, options, tyres=None):
+    """(problem, result) of oracle.ipopt.solve_ipopt(..., log=True, rules=PRODUCT) on the B = 1 instance ``sub``
+    under the configuration ``cfg`` and the solver ``options``.  Shared with make_shift_golden.py."""
     import torch
     torch.set_num_threads(1)
     from mpcracing import workload as wl
     from oracle.ipopt import PRODUCT, solve_ipopt
     from oracle.nlp import MPCProblem
-    _name, _i, kind = CASES[case]
-    cfg, sub = case_config(case), case_inputs(case)
     inst = wl.instance_dicts(sub)[0]
     kw = {}
     if sub["u_init"] is not None:  # MPCProblem shifts last_controls itself: lc[1:] + [lc[-1]] == the columns
         cols = [(float(a), float(s)) for a, s in zip(*sub["u_init"][:, :, 0])]
         kw["last_controls"] = [(0.0, 0.0)] + cols[:-1]
     p = MPCProblem(inst["state0"], inst["s0"], inst["cx"], inst["cy"], inst["max_error"], N=cfg["N"], Ts=cfg["Ts"],
-                   model=cfg["model"], lane_bounds=cfg["lane"], tyres=case_tyres(case), **kw)
-    o = OPTIONS[kind]
-    t0 = time.time()
+                   model=cfg["model"], lane_bounds=cfg["lane"], tyres=tyres, **kw)
+    o = options
     r = solve_ipopt(p, tol=o["tol"], max_iter=o["max_iter"], acceptable_tol=o["acceptable_tol"],
                     acceptable_iter=o["acceptable_iter"], log=True, rules=PRODUCT)
-    log = np.array([[kkt, mu, alpha, delta, th, ph, float(resto)]
-                    for (_k, kkt, mu, alpha, delta, th, ph, resto) in r.log]).reshape(-1, 7)
-    res = dict(log=log, status=int(r.status), iters=int(r.iters), obj=float(r.obj), seconds=time.time() - t0)
+    return p, r
+
+
+def log_rows(r):
+    """The oracle's log as [iterations][7] in LOG_COL order."""
+    return np.array([[kkt, mu, alpha, delta, th, ph, float(resto)]
+                     for (_k, kkt, mu, alpha, delta, th, ph, resto) in r.log]).reshape(-1, 7)
+
+
+def _oracle(case):
+    _name, _i, kind = CASES[case]
+    t0 = time.time()
+    p, r = oracle_solve(case_config(case), case_inputs(case), OPTIONS[kind], case_tyres(case))
+    res = dict(log=log_rows(r), status=int(r.status), iters=int(r.iters), obj=float(r.obj), seconds=time.time() - t0)
     if kind == "whole":
         assert r.status == 0, (case, r.status)
         res["lam_g"] = p.lam_g_ipopt(r.nu, r.lam)
     return res
 
 
+def host_solve(cfg, sub, options, scalar, precision="fp64", tyres=None):
+    """The B = 1 instance ``sub`` solved by a host build of the solver source (every output of
+    tests/host_twin.solve) under ``cfg`` and ``options``.  Shared with make_shift_golden.py."""
+    import host_twin as ht
+    c = ht.config(cfg["N"], cfg["model"], precision, cfg["lane"], cfg["Ts"], **options)
+    return ht.solve(c, sub, tyres=tyres, nthreads=1, scalar=scalar, trace_instance=0, trace_cap=TRACE_CAP,
+                    duals=not scalar)
+
+
 def host_trace(case, scalar, precision="fp64"):
     """The case's solve by a host build of the solver source (every output of tests/host_twin.solve)."""
-    import host_twin as ht
-    cfg = case_config(case)
-    c = ht.config(cfg["N"], cfg["model"], precision, cfg["lane"], cfg["Ts"], **OPTIONS[CASES[case][2]])
-    return ht.solve(c, case_inputs(case), tyres=case_tyres(case), nthreads=1, scalar=scalar, trace_instance=0,
-                    trace_cap=TRACE_CAP, duals=not scalar)
+    return host_solve(case_config(case), case_inputs(case), OPTIONS[CASES[case][2]], scalar, precision,
+                      case_tyres(case))
 
 
 def n_cmp_rule(log, traces, label=""):
