@@ -37,7 +37,8 @@ extern "C" {
    mr_outputs.lam_g / timeline, mr_config without lane_penalty (hard lane rows), status 4 = infeasible;
    102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
    mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout,
-   mr_pid_gains_default, mr_pid_control, mr_pid_drive, mr_pid_segment_times, mr_ga_random, mr_ga_breed) */
+   mr_pid_gains_default, mr_pid_control, mr_pid_drive, mr_pid_segment_times, mr_ga_random, mr_ga_breed,
+   mr_solve_batch_horizons) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -159,6 +160,19 @@ int mr_destroy(mr_handle* h);
    finish first). */
 int mr_set_tyres(mr_handle* h, const double* a_front, double Fz_front, const double* a_back, double Fz_back);
 int mr_solve_batch(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, void* hip_stream);
+/* mr_solve_batch with one horizon per instance (the reference chooses N per call from the car's speed,
+   script/test_mpc.py:32-33).  horizon: device int32 [B], or NULL (= mr_solve_batch, the same code path).
+     horizon[i] = N_i, 1 <= N_i <= cfg.N.  cfg.N stays the LAYOUT horizon: every array keeps the strides
+   documented above (X [6][cfg.N+1][B], U [2][cfg.N][B], S, eC, eL, u_init [2][cfg.N][B],
+   lam_g [13*cfg.N+9][B]).  Instance i is solved exactly as a handle created with N = N_i solves it: it reads
+   u_init[r][k][i] for k < N_i only, writes X / S rows k <= N_i and U / eC / eL rows k < N_i, and its lam_g
+   column holds, in its first 13*N_i+9 rows, the Opti row order of horizon N_i (what the reference's call with
+   that N returns).  Every other row of the instance's columns is NaN.
+     An instance whose horizon[i] is outside [1, cfg.N] is not solved: status MR_STATUS_FAILED, iters 0, NaN in
+   every float output of its columns (obj / kkt / constr_viol / lam_g included where given), nothing written
+   outside its columns; timeline, where given, holds the short span of its workgroup.  The array is read by the kernel only: no host read, no synchronisation. */
+int mr_solve_batch_horizons(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                            void* hip_stream);
 /* Diagnostics: the handle's vehicle dynamics (fp64) at n points, device arrays x [n][6], u [n][2],
    nu [n][6] -> f [n][6], J [n][6*8] (d f / d(x, u)), H [n][36] (packed upper triangle of
    sum_i nu_i d2 f_i / d(x, u)^2); J == NULL evaluates the value-only variant into f.

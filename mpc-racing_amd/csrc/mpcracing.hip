@@ -104,11 +104,26 @@ struct SSInLDS { static constexpr bool value = MR_SS_LDS && sizeof(T) == 4; };
 
 template <typename T, int MODEL>
 __global__ __launch_bounds__(WL, sizeof(T) == 4 ? MR_WAVES_PER_SIMD_F32 : MR_WAVES_PER_SIMD_F64) void mr_wave_kernel(const ProbParams<T>* Pdev, mr_inputs in, mr_outputs out, int B,
-                                                                         T* ws, const int* order) {
+                                                                         T* ws, const int* order,
+                                                                         const int32_t* horizon) {
   __shared__ alignas(16) T lds[LDS_WORDS];
   const int i = order ? order[blockIdx.x] : (int)blockIdx.x;
   const int64_t t_start = out.timeline ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
   Wv w{(int)threadIdx.x};
+  // the instance's horizon (mr_solve_batch_horizons), one scalar per workgroup; 0 = the layout horizon P.N.
+  // Out of range: the instance is not solved (its columns NaN, status failed) -- a wave-uniform exit
+  int Ni = 0;
+  if (horizon) {
+    Ni = __builtin_amdgcn_readfirstlane(horizon[i]);
+    if (!horizon_ok(Ni, Pdev->N)) {
+      nan_unreached(out, B, i, Pdev->N, -1, w.lane, WL);
+      if (out.timeline && threadIdx.x == 0) {  // its (short) span, as for a solved instance
+        out.timeline[i] = t_start;
+        out.timeline[(int64_t)B + i] = (int64_t)__builtin_amdgcn_s_memrealtime();
+      }
+      return;
+    }
+  }
   MR_GLOBAL T* wsi = (MR_GLOBAL T*)(ws + (int64_t)i * ws_words<T>());
   // problem constants: the handle's device copy, read through the constant address space (scalar
   // loads, SGPRs); instance constants in LDS (every lane writes the same values)
@@ -134,11 +149,12 @@ __global__ __launch_bounds__(WL, sizeof(T) == 4 ? MR_WAVES_PER_SIMD_F32 : MR_WAV
   if constexpr (SSL) {
     __shared__ T ssl[SS_WORDS];
     solve_instance_wave<T, MODEL, true, true>(P, in, out, B, i, wsi, (MR_LDS T*)lds, w, (MR_LDS T*)ssl, &Ish,
-                                              slots, (MR_LDS T*)filt_sh);
+                                              slots, (MR_LDS T*)filt_sh, Ni);
   } else {
     solve_instance_wave<T, MODEL, false, true>(P, in, out, B, i, wsi, (MR_LDS T*)lds, w, wsi, &Ish, slots,
-                                               (MR_LDS T*)filt_sh);
+                                               (MR_LDS T*)filt_sh, Ni);
   }
+  if (Ni) nan_unreached(out, B, i, Pdev->N, Ni, w.lane, WL);  // rows beyond the instance's horizon
   if (out.timeline && threadIdx.x == 0) {
     out.timeline[i] = t_start;
     out.timeline[(int64_t)B + i] = (int64_t)__builtin_amdgcn_s_memrealtime();
@@ -268,7 +284,7 @@ static int upload_params(mr_handle* h) {
 }
 
 template <typename T, int MODEL>
-static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, hipStream_t st) {
+static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon, hipStream_t st) {
   const int* order = nullptr;
   if (h->cfg.dispatch_order == 1 && B > 1) {
     hipLaunchKernelGGL(mr_order_kernel, dim3(1), dim3(kOrderThreads), 0, st, in->state0, B, h->order);
@@ -286,7 +302,7 @@ static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, hip
     }
   }
   hipLaunchKernelGGL((mr_wave_kernel<T, MODEL>), dim3(B), dim3(WL), 0, st, (const ProbParams<T>*)h->params_dev, *in,
-                     *out, B, (T*)h->ws, order);
+                     *out, B, (T*)h->ws, order, horizon);
   HIP_TRY(hipGetLastError());
   if (h->cfg.dispatch_order == 2) {  // this solve's iterations: the next call's default hint
     HIP_TRY(hipMemcpyAsync(h->last_iters, out->iters, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, st));
@@ -296,13 +312,14 @@ static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, hip
 }
 
 template <typename T>
-static int dispatch_model(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, hipStream_t st) {
+static int dispatch_model(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                          hipStream_t st) {
   switch (h->cfg.model) {
-    case MR_MODEL_KINEMATIC: return launch<T, MODEL_KIN>(h, B, in, out, st);
-    case MR_MODEL_DYNAMIC: return launch<T, MODEL_DYN>(h, B, in, out, st);
-    case MR_MODEL_BLENDED: return launch<T, MODEL_BLEND>(h, B, in, out, st);
-    case MR_MODEL_BLENDED_PACEJKA: return launch<T, MODEL_BLEND_PACEJKA>(h, B, in, out, st);
-    case MR_MODEL_DYNAMIC_PACEJKA: return launch<T, MODEL_DYN_PACEJKA>(h, B, in, out, st);
+    case MR_MODEL_KINEMATIC: return launch<T, MODEL_KIN>(h, B, in, out, horizon, st);
+    case MR_MODEL_DYNAMIC: return launch<T, MODEL_DYN>(h, B, in, out, horizon, st);
+    case MR_MODEL_BLENDED: return launch<T, MODEL_BLEND>(h, B, in, out, horizon, st);
+    case MR_MODEL_BLENDED_PACEJKA: return launch<T, MODEL_BLEND_PACEJKA>(h, B, in, out, horizon, st);
+    case MR_MODEL_DYNAMIC_PACEJKA: return launch<T, MODEL_DYN_PACEJKA>(h, B, in, out, horizon, st);
   }
   return fail(MR_ERR_ARG, "unknown model");
 }
@@ -793,7 +810,8 @@ int64_t mr_workspace_bytes_per_instance(const mr_handle* h) {
   return h ? (int64_t)ws_bytes_per_instance(h->cfg) : -1;
 }
 
-int mr_solve_batch(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, void* hip_stream) {
+int mr_solve_batch_horizons(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                            void* hip_stream) {
   if (!h || !in || !out) return fail(MR_ERR_ARG, "null argument");
   if (B < 0 || B > h->cfg.max_batch) return fail(MR_ERR_ARG, "B exceeds max_batch");
   if (B == 0) return MR_OK;
@@ -806,8 +824,11 @@ int mr_solve_batch(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out
     return fail(MR_ERR_STATE, "Pacejka model needs mr_set_tyres");
   MR_GUARD_DEVICE(h->cfg.device);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (h->cfg.precision == MR_PREC_FP64) return dispatch_model<double>(h, B, in, out, st);
-  return dispatch_model<float>(h, B, in, out, st);
+  if (h->cfg.precision == MR_PREC_FP64) return dispatch_model<double>(h, B, in, out, horizon, st);
+  return dispatch_model<float>(h, B, in, out, horizon, st);
+}
+int mr_solve_batch(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, void* hip_stream) {
+  return mr_solve_batch_horizons(h, B, in, out, nullptr, hip_stream);
 }
 
 

@@ -40,10 +40,41 @@ MR_HD void taylor_shift4(const double* c_desc, double s0, double* a) {
   for (int j = 0; j < 5; ++j) a[j] = c[j];
 }
 
+// The instance horizon of mr_solve_batch_horizons: horizon[i], or the layout horizon without the array.
+MR_HD int instance_horizon(const int32_t* horizon, int64_t i, int NL) { return horizon ? (int)horizon[i] : NL; }
+MR_HD bool horizon_ok(int N, int NL) { return N >= 1 && N <= NL; }
+
+// NaN in the rows of instance i's float output columns that its horizon N does not reach (include/mpcracing.h
+// mr_solve_batch_horizons): X / S rows k > N, U / eC / eL rows k >= N, lam_g rows >= 13 N + 9.  N = -1: the
+// instance is not solved (horizon out of range) -- every row, the scalars too, status failed, 0 iterations.
+// `lane` of `lanes` cooperating lanes (a wave: its lane of WL; a serial caller: 0 of 1).
+MR_HD void nan_unreached(const mr_outputs& out, int64_t B, int64_t i, int NL, int N, int lane, int lanes) {
+  for (int k = N + 1 + lane; k <= NL; k += lanes) {
+    for (int j = 0; j < 6; ++j) out.X[(j * (NL + 1) + k) * B + i] = NAN;
+    out.S[k * B + i] = NAN;
+  }
+  for (int k = (N < 0 ? 0 : N) + lane; k < NL; k += lanes) {
+    out.U[(0 * NL + k) * B + i] = NAN;
+    out.U[(1 * NL + k) * B + i] = NAN;
+    out.eC[k * B + i] = NAN;
+    out.eL[k * B + i] = NAN;
+  }
+  if (out.lam_g)
+    for (int row = (N < 0 ? 0 : 13 * N + 9) + lane; row < 13 * NL + 9; row += lanes) out.lam_g[(int64_t)row * B + i] = NAN;
+  if (N < 0 && lane == 0) {
+    out.status[i] = MR_STATUS_FAILED;
+    out.iters[i] = 0;
+    if (out.obj) out.obj[i] = NAN;
+    if (out.kkt) out.kkt[i] = NAN;
+    if (out.constr_viol) out.constr_viol[i] = NAN;
+  }
+}
+
 template <typename T, int MODEL>
 MR_HD SolveOut solve_instance(const ProbParams<T>& P, const mr_inputs& in, const mr_outputs& out, int64_t B,
-                              int64_t i, WS<T> W) {
-  const int N = P.N;
+                              int64_t i, WS<T> W, int Ni = 0) {
+  // NL: the layout horizon (the stride of the batch arrays); N: the instance's horizon (0 = the layout horizon)
+  const int NL = P.N, N = Ni ? Ni : NL;
   Inst<T> I;
   const double X0 = in.state0[0 * B + i], Y0 = in.state0[1 * B + i];
   const double s0 = in.s0[i];
@@ -72,22 +103,22 @@ MR_HD SolveOut solve_instance(const ProbParams<T>& P, const mr_inputs& in, const
   I.org[0] = T(X0);
   I.org[1] = T(Y0);
   I.org[2] = T(s0);
-  Solver<T, MODEL> S(P, I, W);
+  Solver<T, MODEL> S(P, I, W, N);
   if (out.trace && out.trace_instance == i) { S.trace = out.trace; S.trace_cap = out.trace_cap; }
-  S.init(in.u_init ? in.u_init + i : nullptr, B);
+  S.init(in.u_init ? in.u_init + i : nullptr, B, NL);
   SolveOut r = S.solve();
   // outputs (the ret tuple of control/MPC.py:166-171), back in global coordinates
   const int b = S.cur;
   for (int k = 0; k <= N; ++k) {
     T z[NZS];
     S.load_z(k, b, z);
-    out.X[(0 * (N + 1) + k) * B + i] = (double)z[0] + X0;
-    out.X[(1 * (N + 1) + k) * B + i] = (double)z[1] + Y0;
-    for (int j = 2; j < 6; ++j) out.X[(j * (N + 1) + k) * B + i] = (double)z[j];
+    out.X[(0 * (NL + 1) + k) * B + i] = (double)z[0] + X0;
+    out.X[(1 * (NL + 1) + k) * B + i] = (double)z[1] + Y0;
+    for (int j = 2; j < 6; ++j) out.X[(j * (NL + 1) + k) * B + i] = (double)z[j];
     out.S[k * B + i] = (double)z[6] + s0;
     if (k < N) {
-      out.U[(0 * N + k) * B + i] = (double)z[11];
-      out.U[(1 * N + k) * B + i] = (double)z[12];
+      out.U[(0 * NL + k) * B + i] = (double)z[11];
+      out.U[(1 * NL + k) * B + i] = (double)z[12];
       Err<T> e;
       errors(I, z[0], z[1], z[6], e, false);
       out.eC[k * B + i] = (double)e.eC;
@@ -99,6 +130,7 @@ MR_HD SolveOut solve_instance(const ProbParams<T>& P, const mr_inputs& in, const
   if (out.obj) out.obj[i] = r.obj - (double)P.lambda_s * s0;  // -lambda_s * S_N in global s
   if (out.kkt) out.kkt[i] = r.kkt;
   if (out.constr_viol) out.constr_viol[i] = r.viol;
+  if (N != NL) nan_unreached(out, B, i, NL, N, 0, 1);
   return r;
 }
 

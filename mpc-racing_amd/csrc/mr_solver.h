@@ -342,9 +342,8 @@ MR_HD constexpr bool oneslot(int j) { return j < 4; }
 MR_HD constexpr int slot_sign(int j) { return (j & 1) ? -1 : 1; }
 
 template <typename T>
-MR_HD void make_row_raw(const ProbParams<T>& P, const Inst<T>& I, int k, int r, const T* z, const Err<T>* e,
+MR_HD void make_row_raw(const ProbParams<T>& P, const Inst<T>& I, int N, int k, int r, const T* z, const Err<T>* e,
                         Row<T>& R) {
-  const int N = P.N;
   R.active = 0; R.n = 0; R.lane = 0; R.c = T(0); R.lo = T(0); R.hi = T(0);
   if (k == N) return;  // terminal stage: only the lane rows (lane_active)
   switch (r) {
@@ -382,8 +381,9 @@ MR_HD void make_row_raw(const ProbParams<T>& P, const Inst<T>& I, int k, int r, 
 }
 
 template <typename T>
-MR_HD void make_row(const ProbParams<T>& P, const Inst<T>& I, int k, int r, const T* z, const Err<T>* e, Row<T>& R) {
-  make_row_raw(P, I, k, r, z, e, R);
+MR_HD void make_row(const ProbParams<T>& P, const Inst<T>& I, int N, int k, int r, const T* z, const Err<T>* e,
+                    Row<T>& R) {
+  make_row_raw(P, I, N, k, r, z, e, R);
   R.lo -= relax_amt(R.lo);
   R.hi += relax_amt(R.hi);
 }
@@ -407,10 +407,10 @@ MR_HD void lane_d(const Inst<T>& I, T eC, T t, T* d) {  // t: the unused slot 14
 // Stage cost (MPC.py:86-98), scaled by obj_scale.  Stage 0 has no cost.
 // ----------------------------------------------------------------------------------------
 template <typename T>
-MR_HD T stage_cost(const ProbParams<T>& P, const Inst<T>& I, int k, const T* z, const Err<T>& e, T sc, T* g, T* H) {
-  // g: gradient (NZ), H: packed Hessian (NH) accumulated; either may be null
+MR_HD T stage_cost(const ProbParams<T>& P, const Inst<T>& I, int N, int k, const T* z, const Err<T>& e, T sc, T* g,
+                   T* H) {
+  // N: the instance's horizon; g: gradient (NZ), H: packed Hessian (NH) accumulated; either may be null
   if (k == 0) return T(0);
-  const int N = P.N;
   T val = T(0);
   // q_v_y * vy^2
   T vy = z[4];
@@ -847,7 +847,8 @@ struct Solver {
   // in both precisions (correction form: eval_sweep)
   double nub[64][NX], wnub[64][NX], anub[64][NX];  // (anub: the stored acceptable point's)
 
-  MR_HD Solver(const ProbParams<T>& P_, const Inst<T>& I_, WS<T> W_) : P(P_), I(I_), W(W_), N(P_.N) {}
+  // N_: the instance's horizon (1 .. P_.N; P_.N is the layout horizon of the batch arrays)
+  MR_HD Solver(const ProbParams<T>& P_, const Inst<T>& I_, WS<T> W_, int N_) : P(P_), I(I_), W(W_), N(N_) {}
 
   MR_HD int zf(int b) const { return b ? WF::Z1 : WF::Z0; }
   MR_HD int sf(int b) const { return b ? WF::S1 : WF::S0; }
@@ -865,7 +866,7 @@ struct Solver {
   // one-sided row values d_j (slots 0..16) of stage k at z; returns row-active mask bits
   MR_HD void row_values(int k, const T* z, const Err<T>& e, T* d, int* act, Row<T>* rows) const {
     for (int r = 0; r < NROW; ++r) {
-      make_row(P, I, k, r, z, &e, rows[r]);
+      make_row(P, I, N, k, r, z, &e, rows[r]);
       act[2 * r] = act[2 * r + 1] = rows[r].active;
       d[2 * r] = rows[r].c - rows[r].lo;
       d[2 * r + 1] = rows[r].hi - rows[r].c;
@@ -890,8 +891,9 @@ struct Solver {
   static MR_HD T ipopt_res(int j, const T* d, const T* t) { return T(slot_sign(j)) * (d[j] - t[j]); }
 
   // ---------------- initialisation (MPC.py:100-131; IPOPT's DefaultIterateInitializer) ----------------
-  // u_init: optional strided [2][N] initial controls of this instance (element (r, k) at u_init[(r*N+k)*ustride])
-  MR_HD void init(const double* u_init, int64_t ustride) {
+  // u_init: optional strided [2][NL] initial controls of this instance (element (r, k) at
+  // u_init[(r*NL+k)*ustride], NL the layout horizon; read for k < N)
+  MR_HD void init(const double* u_init, int64_t ustride, int NL) {
     cur = 0;
     T z[NZS], zn[NX];
     for (int i = 0; i < NZS; ++i) z[i] = T(0);
@@ -901,7 +903,7 @@ struct Solver {
     T gmax = T(0);
     for (int k = 0; k <= N; ++k) {
       if (k < N) {
-        if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(N + k) * ustride]); }
+        if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(NL + k) * ustride]); }
         else { z[11] = I.thr0; z[12] = I.steer0; }
         z[13] = P.Ts * P.v_max;  // S_i = s0 + i*Ts*v_max (MPC.py:127)
       } else {
@@ -914,7 +916,7 @@ struct Solver {
       // objective gradient for the gradient-based scaling
       T g[NZ];
       for (int i = 0; i < NZ; ++i) g[i] = T(0);
-      stage_cost(P, I, k, z, e, T(1), g, (T*)nullptr);
+      stage_cost(P, I, N, k, z, e, T(1), g, (T*)nullptr);
       for (int i = 0; i < NZ; ++i) gmax = mr_max(gmax, mr_abs(g[i]));
       if (k < N) {
         faug<T, MODEL>(P, k, z, zn);
@@ -997,7 +999,7 @@ struct Solver {
         if (delta_var(i)) H[hidx(i, i)] = T(1);
       Err<T> e;
       errors(I, z[0], z[1], z[6], e, false);
-      stage_cost(P, I, k, z, e, sc, g, (T*)nullptr);
+      stage_cost(P, I, N, k, z, e, sc, g, (T*)nullptr);
       T d[NI];
       int act[NI];
       Row<T> rows[NROW];
@@ -1190,7 +1192,7 @@ struct Solver {
         for (int i = 0; i < NZS; ++i) zr[i] = W(k, WF::RZ + i);
         fval += prox_term(I, k, N, z, zr, zeta, gl, H);
       } else {
-        fval += stage_cost(P, I, k, z, e, sc, gl, H);
+        fval += stage_cost(P, I, N, k, z, e, sc, gl, H);
       }
       for (int i = 0; i < NZ; ++i) { g0[i] += gl[i]; st[i] += gl[i]; }
       // inequality rows: lazy dual update, barrier terms
@@ -1829,9 +1831,9 @@ struct Solver {
         T zr[NZS];
         for (int i = 0; i < NZS; ++i) zr[i] = W(k, WF::RZ + i);
         fv += prox_term(I, k, N, zt, zr, zeta, (T*)nullptr, (T*)nullptr);
-        fo += stage_cost(P, I, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
+        fo += stage_cost(P, I, N, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
       } else {
-        fv += stage_cost(P, I, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
+        fv += stage_cost(P, I, N, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
       }
       if (k < N) {
         T xn[NX];
@@ -2099,7 +2101,7 @@ struct Solver {
       row_values(k, z, e, d, act, rows);
       for (int j = 0; j < NI; ++j)
         if (act[j] && yslot(j)) pr = mr_max(pr, mr_abs(d[j] - W(k, sf(cur) + j)));
-      fo_cur += stage_cost(P, I, k, z, e, sc, (T*)nullptr, (T*)nullptr);
+      fo_cur += stage_cost(P, I, N, k, z, e, sc, (T*)nullptr, (T*)nullptr);
     }
     const T mu_r = mr_max(mu, pr);
     for (int k = 0; k <= N; ++k) {
@@ -2378,7 +2380,7 @@ struct Solver {
       for (int i = 0; i < NX; ++i) dd[i] -= nuk[i];
       Err<T> e;
       errors(I, z[0], z[1], z[6], e, false);
-      stage_cost(P, I, k, z, e, sc, st, (T*)nullptr);
+      stage_cost(P, I, N, k, z, e, sc, st, (T*)nullptr);
       T d[NI];
       int act[NI];
       Row<T> rows[NROW];

@@ -195,17 +195,16 @@ MR_HD constexpr int RI(int r, int a) {
 MR_HD constexpr int RS(int a) { return a ? -1 : 1; }
 
 template <typename T>
-MR_HD void row_bounds_raw(const ProbParams<T>& P, const Inst<T>& I, int k, int r, int& act, T& lo, T& hi);
+MR_HD void row_bounds_raw(const ProbParams<T>& P, const Inst<T>& I, int N, int k, int r, int& act, T& lo, T& hi);
 // the bounds as IPOPT uses them (bound_relax_factor, mr_solver.h relax_amt)
 template <typename T>
-MR_HD void row_bounds(const ProbParams<T>& P, const Inst<T>& I, int k, int r, int& act, T& lo, T& hi) {
-  row_bounds_raw(P, I, k, r, act, lo, hi);
+MR_HD void row_bounds(const ProbParams<T>& P, const Inst<T>& I, int N, int k, int r, int& act, T& lo, T& hi) {
+  row_bounds_raw(P, I, N, k, r, act, lo, hi);
   lo -= relax_amt(lo);
   hi += relax_amt(hi);
 }
 template <typename T>
-MR_HD void row_bounds_raw(const ProbParams<T>& P, const Inst<T>& I, int k, int r, int& act, T& lo, T& hi) {
-  const int N = P.N;
+MR_HD void row_bounds_raw(const ProbParams<T>& P, const Inst<T>& I, int N, int k, int r, int& act, T& lo, T& hi) {
   act = 0; lo = T(0); hi = T(0);
   if (k == N) return;
   if (r == 0) { act = 1; lo = P.min_thr; hi = I.d_max; }          // MPC.py:138-139 (class-attribute d_max)
@@ -311,9 +310,10 @@ struct WaveSolver {
   unsigned long long tsub[24] = {};  // diagnostics: sub-phase cycles of the trace instance
 #endif
 
+  // N_: the instance's horizon (1 .. P_.N; P_.N is the layout horizon of the batch arrays)
   MR_HD WaveSolver(const MR_CONST ProbParams<T>& P_, const Inst<T>& I_, Wv w_, MR_GLOBAL T* ws, MR_LDS T* lds_,
-                   typename SSPtr<T, SSL>::type ss_)
-      : P(P_), I(I_), w(w_), ss(ss_), rc(ws + (int64_t)SSF::NF * WL), lds(lds_), N(P_.N), ln(w_.lane) {}
+                   typename SSPtr<T, SSL>::type ss_, int N_)
+      : P(P_), I(I_), w(w_), ss(ss_), rc(ws + (int64_t)SSF::NF * WL), lds(lds_), N(N_), ln(w_.lane) {}
 
   MR_HD auto& S(int f) const { return ss[f * WL + ln]; }
   MR_HD MR_GLOBAL T& Cf(int f) const { return rc[(int64_t)RC_STRIDE * WL + f * WL + ln]; }  // cold field
@@ -345,7 +345,7 @@ struct WaveSolver {
     for (int r = 0; r < NROW; ++r) {
       int a;
       T lo, hi;
-      row_bounds(P, I, k, r, a, lo, hi);
+      row_bounds(P, I, N, k, r, a, lo, hi);
       const T c = row_c(r, z);
       act[2 * r] = act[2 * r + 1] = a;
       d[2 * r] = c - lo;
@@ -358,8 +358,10 @@ struct WaveSolver {
   }
 
   // ---------------- initialisation (MPC.py:100-131) ----------------
-  MR_SWEEP void init(const double* u_init, int64_t ustride) {
+  // u_init: [2][NL] of this instance, NL the layout horizon (mr_solver.h Solver::init); read for k < N
+  MR_SWEEP void init(const double* u_init, int64_t ustride, int NL) {
     MR_UNIFORM_P();
+    const int Nu = wu(w, N);  // the horizon as a scalar for the stage functions (as P.N, which they used to read)
     cur = 0;
     T z[NZS], zn[NX], my[NZS];
     for (int i = 0; i < NZS; ++i) { z[i] = T(0); my[i] = T(0); }
@@ -369,7 +371,7 @@ struct WaveSolver {
     // initial-guess rollout (sequential, wave-uniform); lane k keeps stage k
     for (int k = 0; k <= N; ++k) {
       if (k < N) {
-        if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(N + k) * ustride]); }
+        if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(NL + k) * ustride]); }
         else { z[11] = I.thr0; z[12] = I.steer0; }
         z[13] = P.Ts * P.v_max;  // S_i = s0 + i*Ts*v_max (MPC.py:127)
       } else {
@@ -393,7 +395,7 @@ struct WaveSolver {
       errors(I, my[0], my[1], my[6], e, false);
       T g[NZ];
       for (int i = 0; i < NZ; ++i) g[i] = T(0);
-      stage_cost(P, I, k, my, e, T(1), g, (T*)nullptr);
+      stage_cost(P, I, Nu, k, my, e, T(1), g, (T*)nullptr);
       for (int i = 0; i < NZ; ++i) gmax = mr_max(gmax, mr_abs(g[i]));
       T d[NI];
       int act[NI];
@@ -410,7 +412,7 @@ struct WaveSolver {
         int ra;
         T lo, hi, c;
         if (r < NROW) {
-          row_bounds(P, I, k, r, ra, lo, hi);
+          row_bounds(P, I, Nu, k, r, ra, lo, hi);
           c = row_c(r, my);
         } else {
           hi = I.max_err + relax_amt(I.max_err);
@@ -502,7 +504,7 @@ struct WaveSolver {
         if (delta_var(i)) H[hidx(i, i)] = T(1);
       Err<T> e;
       errors(I, z[0], z[1], z[6], e, false);
-      stage_cost(P, I, k, z, e, sc, g, (T*)nullptr);
+      stage_cost(P, I, N, k, z, e, sc, g, (T*)nullptr);
       T d[NI];
       int act[NI];
       row_values(k, z, e, d, act);
@@ -736,7 +738,7 @@ struct WaveSolver {
         for (int i = 0; i < NZS; ++i) zr[i] = Cf(CSF::RZ + i);
         f_l += prox_term(I, k, N, z, zr, zeta, gl, H);
       } else {
-        f_l += stage_cost(P, I, k, z, e, sc, gl, H);
+        f_l += stage_cost(P, I, N, k, z, e, sc, gl, H);
       }
       for (int i = 0; i < NZ; ++i) { g0[i] += gl[i]; st[i] += gl[i]; S(SSF::GL + i) = gl[i]; }
       T d[NI];
@@ -1752,7 +1754,7 @@ struct WaveSolver {
 #pragma unroll
     for (int r = 0; r < NROW; ++r) {
       int a;
-      row_bounds(P, I, k, r, a, rlo[r], rhi[r]);
+      row_bounds(P, I, N, k, r, a, rlo[r], rhi[r]);
       actm |= (own() && a) ? (3u << (2 * r)) : 0u;
     }
     const T lmax = I.max_err + relax_amt(I.max_err);  // the lane rows' relaxed bound (lane_d)
@@ -1901,9 +1903,9 @@ struct WaveSolver {
         }
         if constexpr (RESTO) {
           f_l += prox_term(I, k, N, zt, zr, zeta, (T*)nullptr, (T*)nullptr);
-          fo_l += stage_cost(P, I, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
+          fo_l += stage_cost(P, I, N, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
         } else {
-          f_l += stage_cost(P, I, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
+          f_l += stage_cost(P, I, N, k, zt, e, sc, (T*)nullptr, (T*)nullptr);
         }
         if (k < N) {
           T xn[NX];
@@ -2400,7 +2402,7 @@ struct WaveSolver {
       for (int r = 0; r < NROW; ++r) {
         int a;
         T lo, hi;
-        row_bounds(P, I, k, r, a, lo, hi);
+        row_bounds(P, I, N, k, r, a, lo, hi);
         act[2 * r] = act[2 * r + 1] = a;
       }
       act[JL] = act[JL + 1] = lane_active(P, k) ? 1 : 0;
@@ -2535,7 +2537,7 @@ struct WaveSolver {
       row_values(k, z, e, d, act);
       for (int j = 0; j < NI; ++j)
         if (act[j] && yslot(j)) pr_l = mr_max(pr_l, mr_abs(d[j] - S(sf(cur) + j)));
-      fo_l = stage_cost(P, I, k, z, e, sc, (T*)nullptr, (T*)nullptr);
+      fo_l = stage_cost(P, I, N, k, z, e, sc, (T*)nullptr, (T*)nullptr);
     }
     // the original objective at the entry point (reported if the restoration phase ends the solve)
     C->fo_cur = wsum(w, fo_l);
@@ -2863,7 +2865,7 @@ struct WaveSolver {
       for (int i = 0; i < NX; ++i) dd[i] -= nuk[i];
       Err<T> e;
       errors(I, z[0], z[1], z[6], e, false);
-      stage_cost(P, I, k, z, e, sc, st, (T*)nullptr);
+      stage_cost(P, I, N, k, z, e, sc, st, (T*)nullptr);
       T d[NI];
       int act[NI];
       row_values(k, z, e, d, act);
@@ -3441,16 +3443,19 @@ struct WaveSolver {
 // Ish: where the instance constants live -- the workgroup's LDS on the device (every lane writes
 // the same values), so the sweeps read them with LDS latency instead of private-stack latency;
 // nullptr = a local (host build).
+// (the layout horizon -- the stride of the batch arrays, mr_config.N -- is S.P.N; the instance's horizon -- its
+// range -- is S.N)
 template <typename Solver>
-MR_HD void run_instance(Solver& S, const mr_inputs& in, const mr_outputs& out, int64_t B, int64_t i, int N,
+MR_HD void run_instance(Solver& S, const mr_inputs& in, const mr_outputs& out, int64_t B, int64_t i,
                         double X0, double Y0, double s0, Wv w);
 
 template <typename T, int MODEL, bool SSL = false, bool OBJ_LDS = false>
 MR_HD void solve_instance_wave(const MR_CONST ProbParams<T>& P, const mr_inputs& in, const mr_outputs& out, int64_t B,
                                int64_t i, MR_GLOBAL T* ws, MR_LDS T* lds, Wv w,
                                typename SSPtr<T, SSL>::type ssp = nullptr, Inst<T>* Ish = nullptr,
-                               void* solver_slots = nullptr, MR_LDS T* filt_sh = nullptr) {
-  const int N = P.N;
+                               void* solver_slots = nullptr, MR_LDS T* filt_sh = nullptr, int Ni = 0) {
+  // Ni: the instance's horizon (wave-uniform, checked by the caller: horizon_ok); 0 = the layout horizon
+  const int N = Ni ? Ni : (int)P.N;
   Inst<T> Iloc;
   Inst<T>& I = Ish ? *Ish : Iloc;
   const double X0 = in.state0[0 * B + i], Y0 = in.state0[1 * B + i];
@@ -3490,14 +3495,14 @@ MR_HD void solve_instance_wave(const MR_CONST ProbParams<T>& P, const mr_inputs&
     // the solver object (a per-lane copy of the wave-uniform iteration state) in the caller's LDS
     // slots: the non-inlined sweeps reach it through `this`, which would otherwise point into the
     // private stack, whose loads take Infinity-Cache / HBM latency
-    Solver* Sp = new ((char*)solver_slots + (size_t)w.lane * sizeof(Solver)) Solver(P, I, w, ws, lds, ssv);
+    Solver* Sp = new ((char*)solver_slots + (size_t)w.lane * sizeof(Solver)) Solver(P, I, w, ws, lds, ssv, N);
 #if MR_DEVICE_BUILD
     Sp->filt = filt_sh;
 #endif
-    run_instance(*Sp, in, out, B, i, N, X0, Y0, s0, w);
+    run_instance(*Sp, in, out, B, i, X0, Y0, s0, w);
   } else {
-    Solver S(P, I, w, ws, lds, ssv);
-    run_instance(S, in, out, B, i, N, X0, Y0, s0, w);
+    Solver S(P, I, w, ws, lds, ssv, N);
+    run_instance(S, in, out, B, i, X0, Y0, s0, w);
   }
 }
 
@@ -3558,35 +3563,37 @@ MR_HD void write_lam_g(Solver& S, const mr_outputs& out, int64_t B, int64_t i, i
 }
 
 template <typename Solver>
-MR_HD void run_instance(Solver& S, const mr_inputs& in, const mr_outputs& out, int64_t B, int64_t i, int N,
+MR_HD void run_instance(Solver& S, const mr_inputs& in, const mr_outputs& out, int64_t B, int64_t i,
                         double X0, double Y0, double s0, Wv w) {
   typedef decltype(S.mu) T;
   const MR_CONST ProbParams<T>& P = S.P;
   const Inst<T>& I = S.I;
   if (out.trace && out.trace_instance == i) { S.trace = out.trace; S.trace_cap = out.trace_cap; }
-  S.init(in.u_init ? in.u_init + i : nullptr, B);
+  S.init(in.u_init ? in.u_init + i : nullptr, B, P.N);
   S.ls_init();
   SolveOut r = S.solve();
   const T viol = S.lane_violation();
+  // both horizons re-read here (a scalar load, an LDS read): nothing of them is live across the sweeps' calls
+  const int NL = ((const ProbParams<T>*)wu_ptr(&S.P))->N, N = wu(w, S.N);
   // outputs (the ret tuple of control/MPC.py:166-171), lane k writes stage k, global coordinates
   if (S.own()) {
     const int k = w.lane;
     T z[NZS];
     S.load_z(S.cur, z);
-    out.X[(0 * (N + 1) + k) * B + i] = (double)z[0] + X0;
-    out.X[(1 * (N + 1) + k) * B + i] = (double)z[1] + Y0;
-    for (int j = 2; j < 6; ++j) out.X[(j * (N + 1) + k) * B + i] = (double)z[j];
+    out.X[(0 * (NL + 1) + k) * B + i] = (double)z[0] + X0;
+    out.X[(1 * (NL + 1) + k) * B + i] = (double)z[1] + Y0;
+    for (int j = 2; j < 6; ++j) out.X[(j * (NL + 1) + k) * B + i] = (double)z[j];
     out.S[k * B + i] = (double)z[6] + s0;
     if (k < N) {
-      out.U[(0 * N + k) * B + i] = (double)z[11];
-      out.U[(1 * N + k) * B + i] = (double)z[12];
+      out.U[(0 * NL + k) * B + i] = (double)z[11];
+      out.U[(1 * NL + k) * B + i] = (double)z[12];
       Err<T> e;
       errors(I, z[0], z[1], z[6], e, false);
       out.eC[k * B + i] = (double)e.eC;
       out.eL[k * B + i] = (double)e.eL;
     }
   }
-  if (out.lam_g) write_lam_g(S, out, B, i, N, w);
+  if (out.lam_g) write_lam_g(S, out, B, i, N, w);  // (Opti row order of horizon N: no layout stride)
   (void)viol;
   if (w.lane == 0) {
     out.status[i] = r.status;

@@ -65,7 +65,7 @@ EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_
            "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout",
            "mr_plant_params_default", "mr_plant_step_params", "mr_plant_rollout",
            "mr_pid_gains_default", "mr_pid_control", "mr_pid_drive", "mr_pid_segment_times", "mr_ga_random",
-           "mr_ga_breed"]
+           "mr_ga_breed", "mr_solve_batch_horizons"]
 
 
 def _bind_product(lib):
@@ -77,6 +77,8 @@ def _bind_product(lib):
     lib.mr_set_tyres.argtypes = [ctypes.c_void_p, _PD, _D, _PD, _D]
     lib.mr_solve_batch.argtypes = [ctypes.c_void_p, _I32, ctypes.POINTER(MRInputs), ctypes.POINTER(MROutputs),
                                    ctypes.c_void_p]
+    lib.mr_solve_batch_horizons.argtypes = [ctypes.c_void_p, _I32, ctypes.POINTER(MRInputs),
+                                            ctypes.POINTER(MROutputs), ctypes.c_void_p, ctypes.c_void_p]
     lib.mr_eval_dynamics.argtypes = [ctypes.c_void_p, _I32] + [ctypes.c_void_p] * 7
     lib.mr_workspace_bytes_per_instance.argtypes = [ctypes.c_void_p]
     lib.mr_workspace_bytes_per_instance.restype = ctypes.c_int64
@@ -169,6 +171,8 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_solve_batch.argtypes = [ctypes.POINTER(MRConfig), _PD, _D, _PD, _D, ctypes.c_int,
                                     ctypes.POINTER(MRInputs), ctypes.POINTER(MROutputs), ctypes.c_int]
     lib.mrh_solve_batch_scalar.argtypes = lib.mrh_solve_batch.argtypes
+    lib.mrh_solve_batch_horizons.argtypes = lib.mrh_solve_batch.argtypes[:-1] + [_PI32, ctypes.c_int]  # host horizon [B]
+    lib.mrh_solve_batch_scalar_horizons.argtypes = lib.mrh_solve_batch_horizons.argtypes
     lib.mrh_eval_dynamics.argtypes = [ctypes.POINTER(MRConfig), _PD, _D, _PD, _D, _PD, _PD, _PD, _PD, _PD, _PD]
     lib.mrh_pacejka.argtypes = [_PD, _D, _D, ctypes.c_int, _PD]
     V, I = ctypes.c_void_p, ctypes.c_int

@@ -70,6 +70,10 @@ class BatchSolver:
         if h is not None:  # int32 [B] (dispatch_order 2), e.g. a previous solve's iters
             out["order_hint"] = (h if isinstance(h, torch.Tensor) else torch.from_numpy(np.asarray(h))).to(
                 self.device, torch.int32).contiguous()
+        n = batch.get("horizon")
+        if n is not None:  # int32 [B]: one horizon per instance (mr_solve_batch_horizons)
+            out["horizon"] = (n if isinstance(n, torch.Tensor) else torch.from_numpy(np.asarray(n))).to(
+                self.device, torch.int32).contiguous()
         for k in _IN_KEYS:
             v = batch.get(k)
             if v is None:
@@ -94,7 +98,11 @@ class BatchSolver:
         return out
 
     def launch(self, dev_in, out, stream=None, trace_instance=-1):
-        """Enqueue one batched solve on ``stream`` (default: torch's current stream); no sync."""
+        """Enqueue one batched solve on ``stream`` (default: torch's current stream); no sync.
+
+        ``dev_in["horizon"]`` (int32 [B] on the device, optional) gives instance i the horizon N_i in 1 .. N: it
+        is solved as a ``BatchSolver(N_i)`` would solve it, inside arrays that keep the strides of N
+        (include/mpcracing.h mr_solve_batch_horizons); rows beyond N_i come back NaN."""
         B = int(dev_in["s0"].shape[0])
         N = self.N
         shapes = {"state0": (8, B), "s0": (B,), "cx": (5, B), "cy": (5, B), "max_error": (B,), "runtime": (5, B),
@@ -110,6 +118,10 @@ class BatchSolver:
         if h is not None and (tuple(h.shape) != (B,) or h.dtype != torch.int32 or not h.is_contiguous()
                               or h.device != self.device):
             raise ValueError(f"input order_hint: expected contiguous int32 ({B},) on {self.device}")
+        n = dev_in.get("horizon")
+        if n is not None and (tuple(n.shape) != (B,) or n.dtype != torch.int32 or not n.is_contiguous()
+                              or n.device != self.device):
+            raise ValueError(f"input horizon: expected contiguous int32 ({B},) on {self.device}")
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         inp = abi.MRInputs(*[ptr(dev_in.get(k)) for k in _IN_KEYS + ("order_hint",)])
         tr = out.get("trace")
@@ -118,8 +130,12 @@ class BatchSolver:
                           int(tr.shape[0]) if tr is not None else 0, ptr(out.get("lam_g")),
                           ptr(out.get("timeline")), ptr(out.get("constr_viol")))
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        self._check(self.lib.mr_solve_batch(self.h, B, ctypes.byref(inp), ctypes.byref(o),
-                                            ctypes.c_void_p(st.cuda_stream)))
+        if n is None:
+            self._check(self.lib.mr_solve_batch(self.h, B, ctypes.byref(inp), ctypes.byref(o),
+                                                ctypes.c_void_p(st.cuda_stream)))
+        else:
+            self._check(self.lib.mr_solve_batch_horizons(self.h, B, ctypes.byref(inp), ctypes.byref(o), ptr(n),
+                                                         ctypes.c_void_p(st.cuda_stream)))
         return out
 
     def solve(self, batch, stream=None, trace_instance=-1, trace_cap=0, duals=False):

@@ -44,7 +44,7 @@ class ClosedLoop:
     def __init__(self, track="shanghai_intl_circuit", B=1, N=15, plant="blend", mpc_model="dyn",
                  precision="fp64", Ts=0.05, dt=0.05, start_control_at=50, lookback=5.0, lookahead=45.0,
                  runtime=(1000.0, 0.85, 50.0, 2.0, 5000.0), device=0, plant_tyres=None, plant_kind=None,
-                 plant_params=None, **solver_kw):
+                 plant_params=None, horizon=None, horizon_lookahead=20.0, horizon_min=5, **solver_kw):
         if start_control_at < 1:
             raise ValueError("start_control_at >= 1: the MPC's yaw rate is a finite difference over one tick")
         self.track = track if isinstance(track, DeviceTrack) else DeviceTrack(track, device=device)
@@ -94,6 +94,28 @@ class ClosedLoop:
         # NLP reads the class attribute d_max (MPC.py:50), which callers reproduce by passing 0.85
         rt = torch.as_tensor(np.asarray(runtime, dtype=np.float64), **f)
         self.runtime = (rt.reshape(5, 1).expand(5, self.B) if rt.numel() == 5 else rt.reshape(5, self.B)).contiguous()
+        # horizon per vehicle (mr_solve_batch_horizons): None -- every vehicle N; "speed" -- each tick, on the
+        # device, the reference's rule N_i = ceil(lookahead / (Ts * v_x)) (script/test_mpc.py:32-33,
+        # agent.py:152-153), clipped to [horizon_min, N]; an int array [B] -- N_i fixed per vehicle.  N stays
+        # the layout of every array; rows beyond N_i are NaN.
+        self.Ts = float(Ts)
+        self.horizon_mode, self.horizon = None, None
+        self.horizon_lookahead, self.horizon_min = float(horizon_lookahead), int(horizon_min)
+        if isinstance(horizon, str):
+            if horizon != "speed":
+                raise ValueError('horizon: None, "speed" or an int array [B]')
+            if not 1 <= self.horizon_min <= self.N:
+                raise ValueError(f"horizon_min must be in 1..N = {self.N}")
+            if not self.horizon_lookahead > 0:
+                raise ValueError("horizon_lookahead must be > 0")
+            self.horizon_mode = "speed"
+        elif horizon is not None:
+            hz = np.asarray(horizon.cpu() if isinstance(horizon, torch.Tensor) else horizon)
+            if hz.shape != (self.B,) or hz.dtype.kind not in "iu" or hz.min() < 1 or hz.max() > self.N:
+                raise ValueError(f"horizon: an int array [{self.B}] with entries in 1..N = {self.N}")
+            self.horizon_mode = "fixed"
+            self.horizon = torch.as_tensor(hz.astype(np.int32), device=self.dev).contiguous()
+        self._k1 = torch.arange(1, self.N + 1, device=self.dev).reshape(self.N, 1)  # k + 1 of the warm-start gather
         self.sol = self.solver.alloc_outputs(self.B)
         self.progress = torch.empty(self.B, **f)
         self.error = torch.empty(self.B, **f)
@@ -116,6 +138,7 @@ class ClosedLoop:
         self.cmd_steer = torch.zeros(self.B, **f)
         self.cmd_brake = torch.zeros(self.B, **f)
         self.last_controls = None
+        self.last_horizon = None  # the horizons of last_controls (horizon modes)
         self.steps = 0
 
     @staticmethod
@@ -154,17 +177,28 @@ class ClosedLoop:
                                             _ptr(self.progress), _ptr(self.error), _ptr(self.cx), _ptr(self.cy),
                                             _ptr(self.max_error), sp))
         controlled = self.steps >= self.start_control_at
+        hz = self.horizon
+        if self.horizon_mode == "speed":
+            hz = torch.clamp(torch.ceil(self.horizon_lookahead / (self.Ts * torch.clamp(vx, min=1e-3))),
+                             self.horizon_min, self.N).to(torch.int32)
         if controlled:
             thr0 = torch.where(self.cmd_brake == 0, self.cmd_throttle, -self.cmd_brake)   # agent.py:149
             state0 = torch.stack([X, Y, yaw, vx, vy, yawdot, thr0, self.cmd_steer]).contiguous()
             u_init = None
             if self.last_controls is not None:  # shifted warm start (MPC.py:120-121)
                 lc = self.last_controls
-                u_init = torch.cat([lc[:, 1:], lc[:, -1:]], dim=1).contiguous()
+                if hz is None:
+                    u_init = torch.cat([lc[:, 1:], lc[:, -1:]], dim=1).contiguous()
+                else:  # across a changed horizon: u_init[:, k, i] = U_prev[:, min(k + 1, N_prev_i - 1), i]
+                    idx = torch.minimum(self._k1, (self.last_horizon.to(torch.int64) - 1).reshape(1, B))
+                    u_init = torch.gather(lc, 1, idx.expand(2, self.N, B)).contiguous()
             dev_in = dict(state0=state0, s0=self.progress, cx=self.cx, cy=self.cy, max_error=self.max_error,
                           runtime=self.runtime, u_init=u_init,
                           # the previous tick's iters, read by the order kernel before this solve writes them
                           order_hint=self.sol["iters"] if self.last_controls is not None else None)
+            if hz is not None:
+                dev_in["horizon"] = hz
+                self.last_horizon = hz
             self.solver.launch(dev_in, self.sol, stream=st)
             U = self.sol["U"]
             self.last_controls = U.clone()
@@ -179,7 +213,7 @@ class ClosedLoop:
         rec = dict(step=self.steps, X=X.clone(), Y=Y.clone(), yaw=yaw.clone(), vx=vx.clone(), vy=vy.clone(),
                    yawdot=yawdot, progress=self.progress.clone(), error=self.error.clone(),
                    cmd_throttle=self.cmd_throttle, cmd_steer=self.cmd_steer, cmd_brake=self.cmd_brake,
-                   controlled=controlled,
+                   controlled=controlled, horizon=hz.clone() if hz is not None else None,
                    status=self.sol["status"].clone() if controlled else None,
                    iters=self.sol["iters"].clone() if controlled else None,
                    predicted_states=self.sol["X"].clone() if controlled else None,
