@@ -143,9 +143,34 @@ typedef struct mr_outputs {
                         workgroup started and finished; NULL to skip */
   double* constr_viol; /* optional [B]: IPOPT's unscaled constraint violation of the returned point (max-norm
                           of the dynamics / initial-state rows and of the rows' bound violations; the
-                          "Constraint violation" IPOPT prints on exit).  Tells a status-3 stop at an
+                          "Constraint violation" IPOPT prints on exit).  Measured, as IPOPT measures it, against
+                          the bounds relaxed by bound_relax_factor: each finite bound b moved outwards by
+                          1e-8 max(1, |b|), so a point up to that far outside a stated bound reports 0 for the
+                          row (the lane rows included, with lane_bounds).  Tells a status-3 stop at an
                           almost-feasible point from a restoration failure.  NULL to skip */
 } mr_outputs;
+/* What obj, kkt, constr_viol and lam_g refer to, by how the solve ended.  X, U, S, eC, eL are always the last
+   iterate the solver holds; obj, constr_viol, eC and eL are that point's (tests/test_gpu_certificate.py re-derives
+   them from X, U, S at every exit) with the exceptions named here:
+     status 0, and status 1 after acceptable_iter acceptable iterations or when the line search fails at an
+       acceptable point: the current iterate of the original problem, its scaled KKT error in kkt, its
+       multipliers in lam_g.
+     status 1 otherwise (the line search failed at an almost feasible point, or the fp32 stall exit at the mu
+       floor): the stored acceptable point restored whole -- X, U, S, every multiplier, and the obj, kkt and
+       constr_viol saved with it; lam_g is that point's, not the abandoned iterate's.
+     status 2 (max_iter): the last evaluated iterate; obj, kkt and constr_viol are its own, lam_g holds its
+       multipliers, which satisfy no tolerance.  If the limit falls inside the restoration phase, see below.
+     status 3 from the original problem (mu floor with a tiny step, no inertia-correct factorisation, or an almost
+       feasible line-search failure without a stored point): the current iterate and its measures; where
+       kkt <= tol only one of IPOPT's unscaled tests (dual_inf_tol, constr_viol_tol, compl_inf_tol) kept it from
+       status 0, and lam_g is as accurate as at status 0.
+     status 3 / 4 / 2 inside the restoration phase: X, U, S are the restoration iterate; obj is the original
+       objective there and constr_viol the original problem's violation there; kkt is the last value the
+       original problem had before the phase; lam_g holds the
+       restoration NLP's multipliers (of the order of |grad f| away from a KKT multiplier, signs not those of the
+       original rows): diagnostic only.
+     status 3 after a non-finite evaluation: X, U, S are the iterate whose evaluation failed; obj, kkt and
+       constr_viol are stale (the previous iterate's; 0 if the first evaluation failed), lam_g unspecified. */
 
 typedef struct mr_handle mr_handle;
 
