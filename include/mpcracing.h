@@ -38,7 +38,7 @@ extern "C" {
    102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
    mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout,
    mr_pid_gains_default, mr_pid_control, mr_pid_drive, mr_pid_segment_times, mr_ga_random, mr_ga_breed,
-   mr_solve_batch_horizons) */
+   mr_solve_batch_horizons, mr_warm, mr_solve_batch_warm, mr_warm_shift) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -198,6 +198,51 @@ int mr_solve_batch(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out
    outside its columns; timeline, where given, holds the short span of its workgroup.  The array is read by the kernel only: no host read, no synchronisation. */
 int mr_solve_batch_horizons(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
                             void* hip_stream);
+/* A caller's primal guess (what opti.set_initial(States, ...) / set_initial(S_hat, ...) give a CasADi user; the
+   reference itself ignores its sol0, control/MPC.py:22).  Device arrays in the layout of mr_outputs.X / S. */
+typedef struct mr_warm {
+  const double* x_init;  /* [6][cfg.N+1][B]  States guess, global coordinates; row k = 0 is never read */
+  const double* s_init;  /* [cfg.N+1][B]     S_hat guess, global progress;    row k = 0 is never read */
+  const int32_t* use;    /* optional [B]: 0 = this instance starts cold; NULL = all warm */
+  int32_t* used;         /* optional [B] out: 1 if the instance started from the guess, else 0 */
+} mr_warm;
+/* mr_solve_batch_horizons from a primal guess.  warm == NULL is mr_solve_batch_horizons (the same code path, the
+   same bits); otherwise x_init and s_init are required.
+     Warm instance: instance i with horizon N_i starts from w0 = (U = u_init rows k < N_i, or (throttle0, steer0)
+   repeated when u_init is NULL; X_0 = state0, S_0 = s0; X_k = x_init[:, k, i] and S_k = s_init[k, i] for
+   k = 1..N_i) instead of the rollout of the controls and S_k = s0 + k Ts v_max (control/MPC.py:120-131).
+   Everything after that is IPOPT's treatment of a user-given x0, as at a cold start: the objective scaling is
+   taken at w0, the slacks are pushed inside their bounds, bound multipliers 1, the least-squares multiplier
+   estimate, mu = 0.1; the dynamics defects of w0 count in the initial constraint violation (the filter's
+   theta_max / theta_min).  No duals, no mu warm start.  The guess is made relative to (state0.x, state0.y, s0) in
+   fp64 before an fp32 handle rounds it.
+     Cold instance: use[i] == 0, or a non-finite value in rows 1..N_i of the instance's x_init / s_init columns
+   (decided by the instance's wavefront on the device).  It has the bits of mr_solve_batch_horizons, and
+   used[i] = 0.  Rows beyond N_i and row 0 of the guess are never read.  use, x_init and s_init are read by the
+   kernel only: no host read, no synchronisation. */
+int mr_solve_batch_warm(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                        const mr_warm* warm, void* hip_stream);
+/* The next tick's guess from the previous tick's outputs, on the device, one lane per instance (the shift of
+   last_controls, control/MPC.py:120-125, extended to the States and S_hat the reference throws away).  Arrays in
+   the handle's layout (NL = cfg.N): X_prev [6][NL+1][B], U_prev [2][NL][B], S_prev [NL+1][B], status_prev [B],
+   horizon_prev / horizon_new int32 [B] or NULL (= NL), state0_new [8][B] (rows 0..5 read), s0_new [B]; outputs
+   u_init [2][NL][B], x_init [6][NL+1][B], s_init [NL+1][B], use int32 [B].  Per instance, Np = previous and
+   Nn = new horizon:
+     u_init[:, k] = U_prev[:, min(k + 1, Np - 1)], k = 0..NL-1 (every row: also the cold start's shifted controls);
+     k = 1..Nn, k + 1 <= Np: x_init[:, k] = X_prev[:, k + 1], s_init[k] = s0_new + (S_prev[k + 1] - S_prev[1])
+       (differences: a progress that wrapped at the lap end between the ticks needs no special case);
+     otherwise: x_init[:, k] = f(x_init[:, k - 1], u_init[:, k - 1]), one step of the handle's MPC model in fp64
+       with its tyres (the value path of mr_eval_dynamics; for k = 1, from state0_new), and
+       s_init[k] = s_init[k - 1] + (S_prev[Np] - S_prev[Np - 1]) (s_init[0] = s0_new);
+     row 0 and rows beyond Nn of x_init / s_init are NaN;
+     use = 1 iff status_prev is 0 or 1, Np >= 2 and every value written to u_init rows k < Nn and x_init / s_init
+       rows 1..Nn is finite (a non-finite value read shows in one written); else 0.
+   A horizon outside [1, NL]: use = 0, x_init / s_init NaN, u_init from Np clamped into [1, NL].  The outputs
+   must not overlap the inputs.  No host read, no synchronisation. */
+int mr_warm_shift(mr_handle* h, int32_t B, const double* X_prev, const double* U_prev, const double* S_prev,
+                  const int32_t* status_prev, const int32_t* horizon_prev, const double* state0_new,
+                  const double* s0_new, const int32_t* horizon_new, double* u_init, double* x_init, double* s_init,
+                  int32_t* use, void* hip_stream);
 /* Diagnostics: the handle's vehicle dynamics (fp64) at n points, device arrays x [n][6], u [n][2],
    nu [n][6] -> f [n][6], J [n][6*8] (d f / d(x, u)), H [n][36] (packed upper triangle of
    sum_i nu_i d2 f_i / d(x, u)^2); J == NULL evaluates the value-only variant into f.

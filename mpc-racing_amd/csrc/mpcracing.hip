@@ -21,6 +21,7 @@
 #include "mr_plantroll.h"
 #include "mr_pid.h"
 #include "mr_ga.h"
+#include "mr_warm.h"
 #include <vector>
 
 using namespace mr;
@@ -105,7 +106,7 @@ struct SSInLDS { static constexpr bool value = MR_SS_LDS && sizeof(T) == 4; };
 template <typename T, int MODEL>
 __global__ __launch_bounds__(WL, sizeof(T) == 4 ? MR_WAVES_PER_SIMD_F32 : MR_WAVES_PER_SIMD_F64) void mr_wave_kernel(const ProbParams<T>* Pdev, mr_inputs in, mr_outputs out, int B,
                                                                          T* ws, const int* order,
-                                                                         const int32_t* horizon) {
+                                                                         const int32_t* horizon, mr_warm warm) {
   __shared__ alignas(16) T lds[LDS_WORDS];
   const int i = order ? order[blockIdx.x] : (int)blockIdx.x;
   const int64_t t_start = out.timeline ? (int64_t)__builtin_amdgcn_s_memrealtime() : 0;
@@ -117,6 +118,7 @@ __global__ __launch_bounds__(WL, sizeof(T) == 4 ? MR_WAVES_PER_SIMD_F32 : MR_WAV
     Ni = __builtin_amdgcn_readfirstlane(horizon[i]);
     if (!horizon_ok(Ni, Pdev->N)) {
       nan_unreached(out, B, i, Pdev->N, -1, w.lane, WL);
+      if (warm.used && threadIdx.x == 0) warm.used[i] = 0;
       if (out.timeline && threadIdx.x == 0) {  // its (short) span, as for a solved instance
         out.timeline[i] = t_start;
         out.timeline[(int64_t)B + i] = (int64_t)__builtin_amdgcn_s_memrealtime();
@@ -149,10 +151,10 @@ __global__ __launch_bounds__(WL, sizeof(T) == 4 ? MR_WAVES_PER_SIMD_F32 : MR_WAV
   if constexpr (SSL) {
     __shared__ T ssl[SS_WORDS];
     solve_instance_wave<T, MODEL, true, true>(P, in, out, B, i, wsi, (MR_LDS T*)lds, w, (MR_LDS T*)ssl, &Ish,
-                                              slots, (MR_LDS T*)filt_sh, Ni);
+                                              slots, (MR_LDS T*)filt_sh, Ni, warm);
   } else {
     solve_instance_wave<T, MODEL, false, true>(P, in, out, B, i, wsi, (MR_LDS T*)lds, w, wsi, &Ish, slots,
-                                               (MR_LDS T*)filt_sh, Ni);
+                                               (MR_LDS T*)filt_sh, Ni, warm);
   }
   if (Ni) nan_unreached(out, B, i, Pdev->N, Ni, w.lane, WL);  // rows beyond the instance's horizon
   if (out.timeline && threadIdx.x == 0) {
@@ -284,7 +286,8 @@ static int upload_params(mr_handle* h) {
 }
 
 template <typename T, int MODEL>
-static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon, hipStream_t st) {
+static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                  const mr_warm& warm, hipStream_t st) {
   const int* order = nullptr;
   if (h->cfg.dispatch_order == 1 && B > 1) {
     hipLaunchKernelGGL(mr_order_kernel, dim3(1), dim3(kOrderThreads), 0, st, in->state0, B, h->order);
@@ -302,7 +305,7 @@ static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, con
     }
   }
   hipLaunchKernelGGL((mr_wave_kernel<T, MODEL>), dim3(B), dim3(WL), 0, st, (const ProbParams<T>*)h->params_dev, *in,
-                     *out, B, (T*)h->ws, order, horizon);
+                     *out, B, (T*)h->ws, order, horizon, warm);
   HIP_TRY(hipGetLastError());
   if (h->cfg.dispatch_order == 2) {  // this solve's iterations: the next call's default hint
     HIP_TRY(hipMemcpyAsync(h->last_iters, out->iters, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, st));
@@ -313,13 +316,13 @@ static int launch(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, con
 
 template <typename T>
 static int dispatch_model(mr_handle* h, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
-                          hipStream_t st) {
+                          const mr_warm& warm, hipStream_t st) {
   switch (h->cfg.model) {
-    case MR_MODEL_KINEMATIC: return launch<T, MODEL_KIN>(h, B, in, out, horizon, st);
-    case MR_MODEL_DYNAMIC: return launch<T, MODEL_DYN>(h, B, in, out, horizon, st);
-    case MR_MODEL_BLENDED: return launch<T, MODEL_BLEND>(h, B, in, out, horizon, st);
-    case MR_MODEL_BLENDED_PACEJKA: return launch<T, MODEL_BLEND_PACEJKA>(h, B, in, out, horizon, st);
-    case MR_MODEL_DYNAMIC_PACEJKA: return launch<T, MODEL_DYN_PACEJKA>(h, B, in, out, horizon, st);
+    case MR_MODEL_KINEMATIC: return launch<T, MODEL_KIN>(h, B, in, out, horizon, warm, st);
+    case MR_MODEL_DYNAMIC: return launch<T, MODEL_DYN>(h, B, in, out, horizon, warm, st);
+    case MR_MODEL_BLENDED: return launch<T, MODEL_BLEND>(h, B, in, out, horizon, warm, st);
+    case MR_MODEL_BLENDED_PACEJKA: return launch<T, MODEL_BLEND_PACEJKA>(h, B, in, out, horizon, warm, st);
+    case MR_MODEL_DYNAMIC_PACEJKA: return launch<T, MODEL_DYN_PACEJKA>(h, B, in, out, horizon, warm, st);
   }
   return fail(MR_ERR_ARG, "unknown model");
 }
@@ -333,6 +336,14 @@ __global__ void mr_eval_dynamics_kernel(ProbParams<double> P, int n, const doubl
     Dyn<double, MODEL>::f(P, x + 6 * i, u + 2 * i, f + 6 * i);
   else
     Dyn<double, MODEL>::fjh(P, x + 6 * i, u + 2 * i, nu + 6 * i, f + 6 * i, J + 48 * i, H + 36 * i);
+}
+
+// One lane per instance (mr_warm.h); fp64 with the handle's constants, whatever the precision of its solves.
+template <int MODEL>
+__global__ __launch_bounds__(64) void mr_warm_shift_kernel(ProbParams<double> P, WarmShiftArgs A) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= A.B) return;
+  warm_shift_instance<MODEL>(P, A, i);
 }
 
 
@@ -810,9 +821,11 @@ int64_t mr_workspace_bytes_per_instance(const mr_handle* h) {
   return h ? (int64_t)ws_bytes_per_instance(h->cfg) : -1;
 }
 
-int mr_solve_batch_horizons(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
-                            void* hip_stream) {
+int mr_solve_batch_warm(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                        const mr_warm* warm, void* hip_stream) {
   if (!h || !in || !out) return fail(MR_ERR_ARG, "null argument");
+  if (warm && (!warm->x_init || !warm->s_init)) return fail(MR_ERR_ARG, "mr_warm needs x_init and s_init");
+  const mr_warm wm = warm ? *warm : mr_warm{nullptr, nullptr, nullptr, nullptr};
   if (B < 0 || B > h->cfg.max_batch) return fail(MR_ERR_ARG, "B exceeds max_batch");
   if (B == 0) return MR_OK;
   if (!in->state0 || !in->s0 || !in->cx || !in->cy || !in->max_error || !in->runtime)
@@ -824,11 +837,46 @@ int mr_solve_batch_horizons(mr_handle* h, int32_t B, const mr_inputs* in, mr_out
     return fail(MR_ERR_STATE, "Pacejka model needs mr_set_tyres");
   MR_GUARD_DEVICE(h->cfg.device);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (h->cfg.precision == MR_PREC_FP64) return dispatch_model<double>(h, B, in, out, horizon, st);
-  return dispatch_model<float>(h, B, in, out, horizon, st);
+  if (h->cfg.precision == MR_PREC_FP64) return dispatch_model<double>(h, B, in, out, horizon, wm, st);
+  return dispatch_model<float>(h, B, in, out, horizon, wm, st);
+}
+int mr_solve_batch_horizons(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                            void* hip_stream) {
+  return mr_solve_batch_warm(h, B, in, out, horizon, nullptr, hip_stream);
 }
 int mr_solve_batch(mr_handle* h, int32_t B, const mr_inputs* in, mr_outputs* out, void* hip_stream) {
-  return mr_solve_batch_horizons(h, B, in, out, nullptr, hip_stream);
+  return mr_solve_batch_warm(h, B, in, out, nullptr, nullptr, hip_stream);
+}
+
+int mr_warm_shift(mr_handle* h, int32_t B, const double* X_prev, const double* U_prev, const double* S_prev,
+                  const int32_t* status_prev, const int32_t* horizon_prev, const double* state0_new,
+                  const double* s0_new, const int32_t* horizon_new, double* u_init, double* x_init, double* s_init,
+                  int32_t* use, void* hip_stream) {
+  if (!h || !X_prev || !U_prev || !S_prev || !status_prev || !state0_new || !s0_new || !u_init || !x_init ||
+      !s_init || !use)
+    return fail(MR_ERR_ARG, "null argument");
+  if (B < 0 || B > h->cfg.max_batch) return fail(MR_ERR_ARG, "B exceeds max_batch");
+  if (B == 0) return MR_OK;
+  const int m = h->cfg.model;
+  if ((m == MR_MODEL_BLENDED_PACEJKA || m == MR_MODEL_DYNAMIC_PACEJKA) && !h->have_tyres)
+    return fail(MR_ERR_STATE, "Pacejka model needs mr_set_tyres");
+  MR_GUARD_DEVICE(h->cfg.device);
+  ProbParams<double> P;
+  fill_params<double>(h->cfg, h->tf, h->tr, P);
+  const WarmShiftArgs A{B, h->cfg.N, X_prev, U_prev, S_prev, status_prev, horizon_prev, state0_new, s0_new,
+                        horizon_new, u_init, x_init, s_init, use};
+  hipStream_t st = (hipStream_t)hip_stream;
+  dim3 grid((B + 63) / 64), block(64);
+  switch (m) {
+    case MR_MODEL_KINEMATIC: hipLaunchKernelGGL(mr_warm_shift_kernel<MODEL_KIN>, grid, block, 0, st, P, A); break;
+    case MR_MODEL_DYNAMIC: hipLaunchKernelGGL(mr_warm_shift_kernel<MODEL_DYN>, grid, block, 0, st, P, A); break;
+    case MR_MODEL_BLENDED: hipLaunchKernelGGL(mr_warm_shift_kernel<MODEL_BLEND>, grid, block, 0, st, P, A); break;
+    case MR_MODEL_BLENDED_PACEJKA: hipLaunchKernelGGL(mr_warm_shift_kernel<MODEL_BLEND_PACEJKA>, grid, block, 0, st, P, A); break;
+    case MR_MODEL_DYNAMIC_PACEJKA: hipLaunchKernelGGL(mr_warm_shift_kernel<MODEL_DYN_PACEJKA>, grid, block, 0, st, P, A); break;
+    default: return fail(MR_ERR_ARG, "unknown model");
+  }
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
 }
 
 

@@ -18,28 +18,31 @@
 #include "mr_pid.h"
 #include "mr_ga.h"
 #include "mr_probe.h"
+#include "mr_warm.h"
 
 using namespace mr;
 
 // Each instance runs as one emulated wavefront (64 fibers, mr_wave_prims.h host_wave_call) on one CPU thread.
 template <typename T, int MODEL>
 static void run(const mr_config& c, const TyreCoef<double>& tf, const TyreCoef<double>& tr, int B,
-                const mr_inputs& in, const mr_outputs& out, const int32_t* horizon, int nthreads) {
+                const mr_inputs& in, const mr_outputs& out, const int32_t* horizon, const mr_warm* warm, int nthreads) {
   ProbParams<T> P;
   fill_params<T>(c, tf, tr, P);
+  const mr_warm wm = warm ? *warm : mr_warm{nullptr, nullptr, nullptr, nullptr};
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
   for (int i = 0; i < B; ++i) {
     // the instance's horizon (mr_wave_kernel): out of range = not solved
     const int Ni = instance_horizon(horizon, i, P.N);
     if (!horizon_ok(Ni, P.N)) {
       nan_unreached(out, B, i, P.N, -1, 0, 1);
+      if (wm.used) wm.used[i] = 0;
       continue;
     }
     // poisoned workspace / LDS: any read-before-write shows up as NaN (device memory is not zeroed)
     std::vector<T> ws((size_t)ws_words<T>(), (T)NAN), lds((size_t)LDS_WORDS, (T)NAN);
     host_wave_call([&](const Wv& w) {
       solve_instance_wave<T, MODEL>(P, in, out, (int64_t)B, (int64_t)i, ws.data(), lds.data(), w, nullptr, nullptr,
-                                    nullptr, nullptr, Ni);
+                                    nullptr, nullptr, Ni, wm);
     });
     if (Ni != P.N) nan_unreached(out, B, i, P.N, Ni, 0, 1);  // (the kernel's lanes share the rows)
   }
@@ -50,7 +53,8 @@ static void run(const mr_config& c, const TyreCoef<double>& tf, const TyreCoef<d
 // (SURVEY §8(d) "C++ fp64 CPU SQP twin").  Per-thread workspace of (N+1) stage records.
 template <typename T, int MODEL>
 static void run_scalar(const mr_config& c, const TyreCoef<double>& tf, const TyreCoef<double>& tr, int B,
-                       const mr_inputs& in, const mr_outputs& out, const int32_t* horizon, int nthreads) {
+                       const mr_inputs& in, const mr_outputs& out, const int32_t* horizon, const mr_warm* warm,
+                       int nthreads) {
   ProbParams<T> P;
   fill_params<T>(c, tf, tr, P);
 #pragma omp parallel num_threads(nthreads > 0 ? nthreads : 1)
@@ -59,8 +63,11 @@ static void run_scalar(const mr_config& c, const TyreCoef<double>& tf, const Tyr
 #pragma omp for schedule(dynamic, 1)
     for (int i = 0; i < B; ++i) {
       const int Ni = instance_horizon(horizon, i, P.N);
-      if (horizon_ok(Ni, P.N)) solve_instance<T, MODEL>(P, in, out, (int64_t)B, (int64_t)i, WS<T>{ws.data(), 1}, Ni);
-      else nan_unreached(out, B, i, P.N, -1, 0, 1);
+      if (horizon_ok(Ni, P.N)) solve_instance<T, MODEL>(P, in, out, (int64_t)B, (int64_t)i, WS<T>{ws.data(), 1}, Ni, warm);
+      else {
+        nan_unreached(out, B, i, P.N, -1, 0, 1);
+        if (warm && warm->used) warm->used[i] = 0;
+      }
     }
   }
 }
@@ -93,15 +100,16 @@ int mrh_config_default(mr_config* c) {
   return 0;
 }
 
-// horizon: host int32 [B] or NULL (include/mpcracing.h mr_solve_batch_horizons)
-int mrh_solve_batch_horizons(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
-                             double Fz_back, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
-                             int nthreads) {
+// horizon: host int32 [B] or NULL; warm: host arrays or NULL (include/mpcracing.h mr_solve_batch_warm)
+int mrh_solve_batch_warm(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
+                         double Fz_back, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                         const mr_warm* warm, int nthreads) {
+  if (warm && (!warm->x_init || !warm->s_init)) return -1;
   TyreCoef<double> tf{}, tr{};
   if (a_front) tf = pacejka_coef(a_front, Fz_front);
   if (a_back) tr = pacejka_coef(a_back, Fz_back);
   if (c->max_iter < 0 || c->max_iter > FCAP - 2) return -1;  // the line-search filter's capacity (mr_create)
-#define MR_CASE(T, M) run<T, M>(*c, tf, tr, B, *in, *out, horizon, nthreads)
+#define MR_CASE(T, M) run<T, M>(*c, tf, tr, B, *in, *out, horizon, warm, nthreads)
 #define MR_MODELS(T)                                                       \
   switch (c->model) {                                                      \
     case MR_MODEL_KINEMATIC: MR_CASE(T, MODEL_KIN); break;                 \
@@ -115,22 +123,51 @@ int mrh_solve_batch_horizons(const mr_config* c, const double* a_front, double F
 #undef MR_CASE
   return 0;
 }
+int mrh_solve_batch_horizons(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
+                             double Fz_back, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                             int nthreads) {
+  return mrh_solve_batch_warm(c, a_front, Fz_front, a_back, Fz_back, B, in, out, horizon, nullptr, nthreads);
+}
 int mrh_solve_batch(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
                     double Fz_back, int B, const mr_inputs* in, mr_outputs* out, int nthreads) {
   return mrh_solve_batch_horizons(c, a_front, Fz_front, a_back, Fz_back, B, in, out, nullptr, nthreads);
 }
 
-int mrh_solve_batch_scalar_horizons(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
-                                    double Fz_back, int B, const mr_inputs* in, mr_outputs* out,
-                                    const int32_t* horizon, int nthreads) {
+int mrh_solve_batch_scalar_warm(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
+                                double Fz_back, int B, const mr_inputs* in, mr_outputs* out, const int32_t* horizon,
+                                const mr_warm* warm, int nthreads) {
+  if (warm && (!warm->x_init || !warm->s_init)) return -1;
   TyreCoef<double> tf{}, tr{};
   if (a_front) tf = pacejka_coef(a_front, Fz_front);
   if (a_back) tr = pacejka_coef(a_back, Fz_back);
   if (c->N < 1 || c->N > 63) return -1;
   if (c->max_iter < 0 || c->max_iter > FCAP - 2) return -1;
-#define MR_CASE(T, M) run_scalar<T, M>(*c, tf, tr, B, *in, *out, horizon, nthreads)
+#define MR_CASE(T, M) run_scalar<T, M>(*c, tf, tr, B, *in, *out, horizon, warm, nthreads)
   if (c->precision == MR_PREC_FP64) { MR_MODELS(double) } else { MR_MODELS(float) }
 #undef MR_CASE
+  return 0;
+}
+int mrh_solve_batch_scalar_horizons(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,
+                                    double Fz_back, int B, const mr_inputs* in, mr_outputs* out,
+                                    const int32_t* horizon, int nthreads) {
+  return mrh_solve_batch_scalar_warm(c, a_front, Fz_front, a_back, Fz_back, B, in, out, horizon, nullptr, nthreads);
+}
+// mr_warm_shift on host arrays (mr_warm.h): the kernel's function, one instance after the other
+int mrh_warm_shift(const mr_config* c, const double* a_front, double Fz_front, const double* a_back, double Fz_back,
+                   int B, const double* X_prev, const double* U_prev, const double* S_prev, const int32_t* status_prev,
+                   const int32_t* horizon_prev, const double* state0_new, const double* s0_new,
+                   const int32_t* horizon_new, double* u_init, double* x_init, double* s_init, int32_t* use) {
+  if (!c || c->model < 0 || c->model > 4 || c->N < 1 || c->N > 63 || B < 0) return -1;
+  if (!X_prev || !U_prev || !S_prev || !status_prev || !state0_new || !s0_new || !u_init || !x_init || !s_init || !use)
+    return -1;
+  TyreCoef<double> tf{}, tr{};
+  if (a_front) tf = pacejka_coef(a_front, Fz_front);
+  if (a_back) tr = pacejka_coef(a_back, Fz_back);
+  ProbParams<double> P;
+  fill_params<double>(*c, tf, tr, P);
+  const WarmShiftArgs A{B, c->N, X_prev, U_prev, S_prev, status_prev, horizon_prev, state0_new, s0_new, horizon_new,
+                        u_init, x_init, s_init, use};
+  for (int i = 0; i < B; ++i) warm_shift_dispatch(c->model, P, A, i);
   return 0;
 }
 int mrh_solve_batch_scalar(const mr_config* c, const double* a_front, double Fz_front, const double* a_back,

@@ -70,9 +70,21 @@ MR_HD void nan_unreached(const mr_outputs& out, int64_t B, int64_t i, int NL, in
   }
 }
 
+// Instance i's guess of a warm solve (include/mpcracing.h mr_warm): none without the struct or with use[i] == 0.
+MR_HD WarmIn warm_of(const mr_warm* warm, int64_t B, int64_t i, double X0, double Y0, double s0) {
+  WarmIn g;
+  if (warm && warm->x_init && (!warm->use || warm->use[i] != 0)) {
+    g.x = warm->x_init + i;
+    g.s = warm->s_init + i;
+    g.stride = B;
+    g.X0 = X0; g.Y0 = Y0; g.s0 = s0;
+  }
+  return g;
+}
+
 template <typename T, int MODEL>
 MR_HD SolveOut solve_instance(const ProbParams<T>& P, const mr_inputs& in, const mr_outputs& out, int64_t B,
-                              int64_t i, WS<T> W, int Ni = 0) {
+                              int64_t i, WS<T> W, int Ni = 0, const mr_warm* warm = nullptr) {
   // NL: the layout horizon (the stride of the batch arrays); N: the instance's horizon (0 = the layout horizon)
   const int NL = P.N, N = Ni ? Ni : NL;
   Inst<T> I;
@@ -105,7 +117,9 @@ MR_HD SolveOut solve_instance(const ProbParams<T>& P, const mr_inputs& in, const
   I.org[2] = T(s0);
   Solver<T, MODEL> S(P, I, W, N);
   if (out.trace && out.trace_instance == i) { S.trace = out.trace; S.trace_cap = out.trace_cap; }
-  S.init(in.u_init ? in.u_init + i : nullptr, B, NL);
+  const WarmIn g = warm_of(warm, B, i, X0, Y0, s0);
+  S.init(in.u_init ? in.u_init + i : nullptr, B, NL, &g);
+  if (warm && warm->used) warm->used[i] = S.warm_used ? 1 : 0;
   SolveOut r = S.solve();
   // outputs (the ret tuple of control/MPC.py:166-171), back in global coordinates
   const int b = S.cur;

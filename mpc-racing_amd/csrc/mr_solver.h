@@ -195,6 +195,40 @@ struct WS {
   MR_HD T& operator()(int k, int f) const { return base[((int64_t)k * WF::NF + f) * stride]; }
 };
 
+// The caller's primal guess of one instance (include/mpcracing.h mr_warm): States row k at
+// x[(j * (NL + 1) + k) * stride], S_hat row k at s[k * stride], both global; (X0, Y0, s0) the solver origin the
+// rows are taken relative to, in fp64 before the cast to T.  x == nullptr: a cold start.
+struct WarmIn {
+  const double* x = nullptr;
+  const double* s = nullptr;
+  int64_t stride = 0;
+  double X0 = 0.0, Y0 = 0.0, s0 = 0.0;
+};
+MR_HD bool finite_f64(double v) {
+  return (__builtin_bit_cast(unsigned long long, v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+// Row k (1 .. N) of a guess: finite?
+MR_HD bool warm_row_finite(const WarmIn& g, int NL, int k) {
+  bool ok = finite_f64(g.s[(int64_t)k * g.stride]);
+  for (int j = 0; j < 6; ++j) ok = ok && finite_f64(g.x[((int64_t)j * (NL + 1) + k) * g.stride]);
+  return ok;
+}
+// Stage k's slots 0..6 (X relative to the origin, S relative to s0) from row k of a guess, k >= 1
+template <typename T>
+MR_HD void warm_row(const WarmIn& g, int NL, int k, T* z) {
+  z[0] = T(g.x[((int64_t)0 * (NL + 1) + k) * g.stride] - g.X0);
+  z[1] = T(g.x[((int64_t)1 * (NL + 1) + k) * g.stride] - g.Y0);
+  for (int j = 2; j < 6; ++j) z[j] = T(g.x[((int64_t)j * (NL + 1) + k) * g.stride]);
+  z[6] = T(g.s[(int64_t)k * g.stride] - g.s0);
+}
+// Delta-S of stage k (< N) of a guess, S_{k+1} - S_k with S_0 = s0, of the stored (relative, T) values: the
+// stage's S row z[6] + z[13] - z'[6] then starts at its rounding
+template <typename T>
+MR_HD T warm_ds(const WarmIn& g, int k) {
+  const T a = k == 0 ? T(0) : T(g.s[(int64_t)k * g.stride] - g.s0);
+  return T(g.s[(int64_t)(k + 1) * g.stride] - g.s0) - a;
+}
+
 // ----------------------------------------------------------------------------------------
 // Model dispatch
 // ----------------------------------------------------------------------------------------
@@ -841,6 +875,7 @@ struct Solver {
   T fo_acc = T(0), fo_cur = T(0);  // original (scaled) objective of the last trial point / the current iterate
   bool have_acc = false;  // an acceptable iterate is stored (AZ)
   bool resto_first = false;  // the restoration phase's first iteration (no barrier update)
+  bool warm_used = false;  // init started from the caller's primal guess
   double* trace = nullptr;  // optional per-iteration record (diagnostics)
   int trace_cap = 0;
   // the dynamics rows' multipliers nu_k (x_k = F(x_{k-1}, u_{k-1}), k >= 1) and their watchdog copy, fp64
@@ -893,19 +928,24 @@ struct Solver {
   // ---------------- initialisation (MPC.py:100-131; IPOPT's DefaultIterateInitializer) ----------------
   // u_init: optional strided [2][NL] initial controls of this instance (element (r, k) at
   // u_init[(r*NL+k)*ustride], NL the layout horizon; read for k < N)
-  MR_HD void init(const double* u_init, int64_t ustride, int NL) {
+  // wg: optional primal guess (include/mpcracing.h mr_warm): States / S_hat rows 1..N replace the rollout and the
+  // S ramp; a non-finite value in those rows makes the start cold.  warm_used records which start was taken.
+  MR_HD void init(const double* u_init, int64_t ustride, int NL, const WarmIn* wg = nullptr) {
     cur = 0;
+    bool warm = wg && wg->x;
+    for (int k = 1; warm && k <= N; ++k) warm = warm_row_finite(*wg, NL, k);
+    warm_used = warm;
     T z[NZS], zn[NX];
     for (int i = 0; i < NZS; ++i) z[i] = T(0);
     for (int i = 0; i < 6; ++i) z[i] = I.x0[i];
     z[7] = I.has_thr0 ? I.thr0 : T(0);
     z[8] = I.has_steer0 ? I.steer0 : T(0);
-    T gmax = T(0);
+    T gmax = T(0), defect = T(0);
     for (int k = 0; k <= N; ++k) {
       if (k < N) {
         if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(NL + k) * ustride]); }
         else { z[11] = I.thr0; z[12] = I.steer0; }
-        z[13] = P.Ts * P.v_max;  // S_i = s0 + i*Ts*v_max (MPC.py:127)
+        z[13] = warm ? warm_ds<T>(*wg, k) : P.Ts * P.v_max;  // cold: S_i = s0 + i*Ts*v_max (MPC.py:127)
       } else {
         z[11] = z[12] = z[13] = T(0);
       }
@@ -920,6 +960,13 @@ struct Solver {
       for (int i = 0; i < NZ; ++i) gmax = mr_max(gmax, mr_abs(g[i]));
       if (k < N) {
         faug<T, MODEL>(P, k, z, zn);
+        if (warm) {
+          // the guess's row k + 1 in place of the model's step: the step is the row's defect, part of theta_0
+          // (zero at a cold start); the p and w slots stay the step's (they copy the controls)
+          T zw[7];
+          warm_row(*wg, NL, k + 1, zw);
+          for (int i = 0; i < 7; ++i) { defect += mr_abs(zn[i] - zw[i]); zn[i] = zw[i]; }
+        }
         for (int i = 0; i < NX; ++i) z[i] = zn[i];
       }
     }
@@ -966,6 +1013,7 @@ struct Solver {
       }
       for (int i = 0; i < NX; ++i) { nub[k][i] = 0.0; W(k, WF::DNU + i) = T(0); }
     }
+    if (warm) th += defect;  // IPOPT's theta_0 = ||c(x_0)||_1 + ||d(x_0) - s_0||_1
     mu = T(0.1);
     delta_last = T(0);
     alpha_p = alpha_d = T(0);

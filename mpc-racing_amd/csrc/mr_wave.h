@@ -359,35 +359,69 @@ struct WaveSolver {
 
   // ---------------- initialisation (MPC.py:100-131) ----------------
   // u_init: [2][NL] of this instance, NL the layout horizon (mr_solver.h Solver::init); read for k < N
-  MR_SWEEP void init(const double* u_init, int64_t ustride, int NL) {
+  // xw, sw: this instance's primal guess (mr_solver.h WarmIn, stride ustride, origin X0, Y0, s0), or null.  A
+  // guess with a non-finite value in rows 1..N is not taken (a wave vote).  Returns 1 if the start is the guess.
+  MR_SWEEP int init(const double* u_init, int64_t ustride, int NL, const double* xw, const double* sw, double X0,
+                    double Y0, double s0) {
     MR_UNIFORM_P();
     const int Nu = wu(w, N);  // the horizon as a scalar for the stage functions (as P.N, which they used to read)
     cur = 0;
     T z[NZS], zn[NX], my[NZS];
     for (int i = 0; i < NZS; ++i) { z[i] = T(0); my[i] = T(0); }
-    for (int i = 0; i < 6; ++i) z[i] = I.x0[i];
-    z[7] = I.has_thr0 ? I.thr0 : T(0);
-    z[8] = I.has_steer0 ? I.steer0 : T(0);
-    // initial-guess rollout (sequential, wave-uniform); lane k keeps stage k
-    for (int k = 0; k <= N; ++k) {
-      if (k < N) {
-        if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(NL + k) * ustride]); }
-        else { z[11] = I.thr0; z[12] = I.steer0; }
-        z[13] = P.Ts * P.v_max;  // S_i = s0 + i*Ts*v_max (MPC.py:127)
-      } else {
-        z[11] = z[12] = z[13] = T(0);
+    WarmIn wg;
+    wg.x = xw; wg.s = sw; wg.stride = ustride; wg.X0 = X0; wg.Y0 = Y0; wg.s0 = s0;
+    bool warm = false;
+    if (xw) warm = wall(w, !(ln >= 1 && ln <= N) || warm_row_finite(wg, NL, ln));
+    T defect = T(0);
+    if (warm) {
+      // lane k loads its own stage and fills the stage vector as the rollout below would have: p_k = u_{k-1}
+      // (p_0 = throttle0 / steer0), the frozen copy w of U[:, 0] from stage 1 on, Delta-S = S_{k+1} - S_k
+      const int k = ln;
+      auto uk = [&](int r, int kk) {
+        return u_init ? T(u_init[(int64_t)(r * NL + kk) * ustride]) : (r == 0 ? I.thr0 : I.steer0);
+      };
+      if (own()) {
+        if (k >= 1) warm_row(wg, NL, k, my);
+        else
+          for (int i = 0; i < 6; ++i) my[i] = I.x0[i];
+        my[7] = k >= 1 ? uk(0, k - 1) : (I.has_thr0 ? I.thr0 : T(0));
+        my[8] = k >= 1 ? uk(1, k - 1) : (I.has_steer0 ? I.steer0 : T(0));
+        my[9] = k >= 1 ? uk(0, 0) : T(0);
+        my[10] = k >= 1 ? uk(1, 0) : T(0);
+        if (k < N) { my[11] = uk(0, k); my[12] = uk(1, k); my[13] = warm_ds<T>(wg, k); }
       }
-      Err<T> e;
-      errors(I, z[0], z[1], z[6], e, false);
-      z[14] = T(0);  // (the stage vector's slot 14 is unused)
-      if (ln == k)
-        for (int i = 0; i < NZS; ++i) my[i] = z[i];
+      // the dynamics defects of the guess (zero after a rollout): part of theta_0 below
+      T nx[7];
+      for (int i = 0; i < 7; ++i) nx[i] = wnext(w, my[i]);
       if (k < N) {
-        faug<T, MODEL>(P, k, z, zn);
-        for (int i = 0; i < NX; ++i) z[i] = zn[i];
+        faug<T, MODEL>(P, k, my, zn);
+        for (int i = 0; i < 7; ++i) defect += mr_abs(zn[i] - nx[i]);
+      }
+    } else {
+      for (int i = 0; i < 6; ++i) z[i] = I.x0[i];
+      z[7] = I.has_thr0 ? I.thr0 : T(0);
+      z[8] = I.has_steer0 ? I.steer0 : T(0);
+      // initial-guess rollout (sequential, wave-uniform); lane k keeps stage k
+      for (int k = 0; k <= N; ++k) {
+        if (k < N) {
+          if (u_init) { z[11] = T(u_init[(int64_t)k * ustride]); z[12] = T(u_init[(int64_t)(NL + k) * ustride]); }
+          else { z[11] = I.thr0; z[12] = I.steer0; }
+          z[13] = P.Ts * P.v_max;  // S_i = s0 + i*Ts*v_max (MPC.py:127)
+        } else {
+          z[11] = z[12] = z[13] = T(0);
+        }
+        Err<T> e;
+        errors(I, z[0], z[1], z[6], e, false);
+        z[14] = T(0);  // (the stage vector's slot 14 is unused)
+        if (ln == k)
+          for (int i = 0; i < NZS; ++i) my[i] = z[i];
+        if (k < N) {
+          faug<T, MODEL>(P, k, z, zn);
+          for (int i = 0; i < NX; ++i) z[i] = zn[i];
+        }
       }
     }
-    T gmax = T(0), th = T(0);
+    T gmax = T(0), th = defect;
     if (own()) {
       const int k = ln;
       for (int i = 0; i < NZS; ++i) S(SSF::Z0 + i) = my[i];
@@ -477,6 +511,7 @@ struct WaveSolver {
     C->in_soft = 0;
     C->soft_count = 0;
     C->delta_it = T(0);
+    return warm ? 1 : 0;
   }
 
   // IPOPT's least-square multipliers at the initial point (mr_solver.h Solver::ls_init): the stage QP
@@ -3447,14 +3482,16 @@ struct WaveSolver {
 // range -- is S.N)
 template <typename Solver>
 MR_HD void run_instance(Solver& S, const mr_inputs& in, const mr_outputs& out, int64_t B, int64_t i,
-                        double X0, double Y0, double s0, Wv w);
+                        double X0, double Y0, double s0, Wv w, const mr_warm& warm);
 
 template <typename T, int MODEL, bool SSL = false, bool OBJ_LDS = false>
 MR_HD void solve_instance_wave(const MR_CONST ProbParams<T>& P, const mr_inputs& in, const mr_outputs& out, int64_t B,
                                int64_t i, MR_GLOBAL T* ws, MR_LDS T* lds, Wv w,
                                typename SSPtr<T, SSL>::type ssp = nullptr, Inst<T>* Ish = nullptr,
-                               void* solver_slots = nullptr, MR_LDS T* filt_sh = nullptr, int Ni = 0) {
+                               void* solver_slots = nullptr, MR_LDS T* filt_sh = nullptr, int Ni = 0,
+                               const mr_warm& warm = mr_warm{nullptr, nullptr, nullptr, nullptr}) {
   // Ni: the instance's horizon (wave-uniform, checked by the caller: horizon_ok); 0 = the layout horizon
+  // warm: the batch's primal guess (include/mpcracing.h mr_warm; x_init null = none)
   const int N = Ni ? Ni : (int)P.N;
   Inst<T> Iloc;
   Inst<T>& I = Ish ? *Ish : Iloc;
@@ -3499,10 +3536,10 @@ MR_HD void solve_instance_wave(const MR_CONST ProbParams<T>& P, const mr_inputs&
 #if MR_DEVICE_BUILD
     Sp->filt = filt_sh;
 #endif
-    run_instance(*Sp, in, out, B, i, X0, Y0, s0, w);
+    run_instance(*Sp, in, out, B, i, X0, Y0, s0, w, warm);
   } else {
     Solver S(P, I, w, ws, lds, ssv, N);
-    run_instance(S, in, out, B, i, X0, Y0, s0, w);
+    run_instance(S, in, out, B, i, X0, Y0, s0, w, warm);
   }
 }
 
@@ -3564,12 +3601,15 @@ MR_HD void write_lam_g(Solver& S, const mr_outputs& out, int64_t B, int64_t i, i
 
 template <typename Solver>
 MR_HD void run_instance(Solver& S, const mr_inputs& in, const mr_outputs& out, int64_t B, int64_t i,
-                        double X0, double Y0, double s0, Wv w) {
+                        double X0, double Y0, double s0, Wv w, const mr_warm& warm) {
   typedef decltype(S.mu) T;
   const MR_CONST ProbParams<T>& P = S.P;
   const Inst<T>& I = S.I;
   if (out.trace && out.trace_instance == i) { S.trace = out.trace; S.trace_cap = out.trace_cap; }
-  S.init(in.u_init ? in.u_init + i : nullptr, B, P.N);
+  const bool want = warm.x_init && (!warm.use || warm.use[i] != 0);
+  const int used = S.init(in.u_init ? in.u_init + i : nullptr, B, P.N, want ? warm.x_init + i : nullptr,
+                          want ? warm.s_init + i : nullptr, X0, Y0, s0);
+  if (warm.used && w.lane == 0) warm.used[i] = used;
   S.ls_init();
   SolveOut r = S.solve();
   const T viol = S.lane_violation();

@@ -50,6 +50,10 @@ class MROutputs(ctypes.Structure):
                                                            ("constr_viol", ctypes.c_void_p)]
 
 
+class MRWarm(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x_init", "s_init", "use", "used")]
+
+
 class MRTyrefitConfig(ctypes.Structure):
     _fields_ = [(n, _I32) for n in ("kind", "optimizer", "epochs", "patience")] + \
                [(n, _D) for n in ("factor", "m", "Iz", "lf", "lr", "T_max", "r_wheel", "C_wheel", "R", "rho", "C_d",
@@ -65,7 +69,7 @@ EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_
            "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout",
            "mr_plant_params_default", "mr_plant_step_params", "mr_plant_rollout",
            "mr_pid_gains_default", "mr_pid_control", "mr_pid_drive", "mr_pid_segment_times", "mr_ga_random",
-           "mr_ga_breed", "mr_solve_batch_horizons"]
+           "mr_ga_breed", "mr_solve_batch_horizons", "mr_solve_batch_warm", "mr_warm_shift"]
 
 
 def _bind_product(lib):
@@ -79,6 +83,9 @@ def _bind_product(lib):
                                    ctypes.c_void_p]
     lib.mr_solve_batch_horizons.argtypes = [ctypes.c_void_p, _I32, ctypes.POINTER(MRInputs),
                                             ctypes.POINTER(MROutputs), ctypes.c_void_p, ctypes.c_void_p]
+    lib.mr_solve_batch_warm.argtypes = [ctypes.c_void_p, _I32, ctypes.POINTER(MRInputs), ctypes.POINTER(MROutputs),
+                                        ctypes.c_void_p, ctypes.POINTER(MRWarm), ctypes.c_void_p]
+    lib.mr_warm_shift.argtypes = [ctypes.c_void_p, _I32] + [ctypes.c_void_p] * 13
     lib.mr_eval_dynamics.argtypes = [ctypes.c_void_p, _I32] + [ctypes.c_void_p] * 7
     lib.mr_workspace_bytes_per_instance.argtypes = [ctypes.c_void_p]
     lib.mr_workspace_bytes_per_instance.restype = ctypes.c_int64
@@ -173,6 +180,10 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_solve_batch_scalar.argtypes = lib.mrh_solve_batch.argtypes
     lib.mrh_solve_batch_horizons.argtypes = lib.mrh_solve_batch.argtypes[:-1] + [_PI32, ctypes.c_int]  # host horizon [B]
     lib.mrh_solve_batch_scalar_horizons.argtypes = lib.mrh_solve_batch_horizons.argtypes
+    # host horizon [B], then the guess (host arrays in an MRWarm) or NULL
+    lib.mrh_solve_batch_warm.argtypes = lib.mrh_solve_batch.argtypes[:-1] + [_PI32, ctypes.POINTER(MRWarm), ctypes.c_int]
+    lib.mrh_solve_batch_scalar_warm.argtypes = lib.mrh_solve_batch_warm.argtypes
+    lib.mrh_warm_shift.argtypes = [ctypes.POINTER(MRConfig), _PD, _D, _PD, _D, ctypes.c_int] + [ctypes.c_void_p] * 12
     lib.mrh_eval_dynamics.argtypes = [ctypes.POINTER(MRConfig), _PD, _D, _PD, _D, _PD, _PD, _PD, _PD, _PD, _PD]
     lib.mrh_pacejka.argtypes = [_PD, _D, _D, ctypes.c_int, _PD]
     V, I = ctypes.c_void_p, ctypes.c_int

@@ -11,7 +11,9 @@ first control; before that it applies (0.5, 0.0).  SURVEY §8(f) rank 1: the sam
 Here every tick is four device steps on one stream, with no host synchronisation:
 
 1. ``mr_agent_sense``  (csrc/mr_agent.h)  progress, error, cx, cy, max_error for all vehicles;
-2. input glue (torch ops on the device): state0 rows, shifted warm start (MPC.py:120-121);
+2. input glue (torch ops on the device): state0 rows, shifted warm start (MPC.py:120-121) -- with
+   ``warm_start="primal"`` one ``mr_warm_shift`` launch instead, which also shifts the previous States and
+   S_hat into the next solve's primal guess (``mr_solve_batch_warm``);
 3. ``mr_solve_batch``  (csrc/mr_wave.h)   the B MPC solves, one wavefront each;
 4. ``mr_plant_step``   (csrc/mr_plant.h)  one plant step per vehicle with the applied command
    (``plant="learned"``: ``mr_vehicle_step``, csrc/mr_rollout.h -- the one-step model of the tyre fit,
@@ -44,7 +46,8 @@ class ClosedLoop:
     def __init__(self, track="shanghai_intl_circuit", B=1, N=15, plant="blend", mpc_model="dyn",
                  precision="fp64", Ts=0.05, dt=0.05, start_control_at=50, lookback=5.0, lookahead=45.0,
                  runtime=(1000.0, 0.85, 50.0, 2.0, 5000.0), device=0, plant_tyres=None, plant_kind=None,
-                 plant_params=None, horizon=None, horizon_lookahead=20.0, horizon_min=5, **solver_kw):
+                 plant_params=None, horizon=None, horizon_lookahead=20.0, horizon_min=5, warm_start=None,
+                 **solver_kw):
         if start_control_at < 1:
             raise ValueError("start_control_at >= 1: the MPC's yaw rate is a finite difference over one tick")
         self.track = track if isinstance(track, DeviceTrack) else DeviceTrack(track, device=device)
@@ -115,6 +118,15 @@ class ClosedLoop:
                 raise ValueError(f"horizon: an int array [{self.B}] with entries in 1..N = {self.N}")
             self.horizon_mode = "fixed"
             self.horizon = torch.as_tensor(hz.astype(np.int32), device=self.dev).contiguous()
+        # warm_start: None -- the reference's start (shifted controls rolled out, S ramp, MPC.py:120-131);
+        # "primal" -- from the second controlled tick on, the previous solution shifted on the device
+        # (mr_warm_shift) as the guess of States and S_hat too (mr_solve_batch_warm)
+        if warm_start not in (None, "primal"):
+            raise ValueError('warm_start: None or "primal"')
+        self.warm_start = warm_start
+        if warm_start:
+            self._warm = self.solver.alloc_warm(self.B)
+            self._warm_used = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
         self._k1 = torch.arange(1, self.N + 1, device=self.dev).reshape(self.N, 1)  # k + 1 of the warm-start gather
         self.sol = self.solver.alloc_outputs(self.B)
         self.progress = torch.empty(self.B, **f)
@@ -185,7 +197,13 @@ class ClosedLoop:
             thr0 = torch.where(self.cmd_brake == 0, self.cmd_throttle, -self.cmd_brake)   # agent.py:149
             state0 = torch.stack([X, Y, yaw, vx, vy, yawdot, thr0, self.cmd_steer]).contiguous()
             u_init = None
-            if self.last_controls is not None:  # shifted warm start (MPC.py:120-121)
+            warm = None
+            if self.warm_start and self.last_controls is not None:
+                # self.sol still holds the previous tick's solution; the solve below overwrites it after the shift
+                warm = self.solver.warm_shift(self.sol, state0, self.progress, self.last_horizon, hz,
+                                              out=self._warm, stream=st)
+                u_init = warm["u_init"]
+            elif self.last_controls is not None:  # shifted warm start (MPC.py:120-121)
                 lc = self.last_controls
                 if hz is None:
                     u_init = torch.cat([lc[:, 1:], lc[:, -1:]], dim=1).contiguous()
@@ -199,6 +217,11 @@ class ClosedLoop:
             if hz is not None:
                 dev_in["horizon"] = hz
                 self.last_horizon = hz
+            if warm is not None:
+                dev_in.update(x_init=warm["x_init"], s_init=warm["s_init"], warm_use=warm["warm_use"])
+                self.sol["warm_used"] = self._warm_used
+            elif self.warm_start:
+                self._warm_used.zero_()  # the first controlled tick is cold
             self.solver.launch(dev_in, self.sol, stream=st)
             U = self.sol["U"]
             self.last_controls = U.clone()
@@ -216,6 +239,7 @@ class ClosedLoop:
                    controlled=controlled, horizon=hz.clone() if hz is not None else None,
                    status=self.sol["status"].clone() if controlled else None,
                    iters=self.sol["iters"].clone() if controlled else None,
+                   warm_used=self._warm_used.clone() if controlled and self.warm_start else None,
                    predicted_states=self.sol["X"].clone() if controlled else None,
                    controls=self.last_controls if controlled else None,
                    s_hat=self.sol["S"].clone() if controlled else None,

@@ -52,13 +52,14 @@ def crossing_times(prog, s_start, s_end, length, dt):
 
 def evaluate_population(track, population, bounds, ticks, v0=15.0, N=15, precision="fp64", plant="blend",
                         dt=0.05, d_max_class_attribute=True, horizon=None, horizon_lookahead=20.0, horizon_min=5,
-                        **solver_kw):
+                        warm_start=None, **solver_kw):
     """Segment times [P][K] of P individuals ([P][5] runtime vectors) on K segments (bounds [K+1]).
 
     d_max_class_attribute: the reference's NLP ignores the runtime d_max (MPC.py:50 reads the
     class attribute 0.85); True reproduces that.
     horizon, horizon_lookahead, horizon_min: ClosedLoop's (None, "speed" or an int array [P*K], vehicle =
-    individual * K + segment)."""
+    individual * K + segment).
+    warm_start: ClosedLoop's (None, or "primal": each tick starts from the previous solution, shifted)."""
     pop = np.asarray(population, dtype=np.float64).reshape(-1, 5)
     P, K = pop.shape[0], len(bounds) - 1
     starts = np.asarray(bounds[:-1], dtype=np.float64)
@@ -69,7 +70,7 @@ def evaluate_population(track, population, bounds, ticks, v0=15.0, N=15, precisi
     s0 = np.tile(starts, P)
     loop = ClosedLoop(track, B=P * K, N=N, plant=plant, precision=precision, dt=dt, start_control_at=1,
                       runtime=rt, horizon=horizon, horizon_lookahead=horizon_lookahead, horizon_min=horizon_min,
-                      **solver_kw)
+                      warm_start=warm_start, **solver_kw)
     x0 = ClosedLoop.start_states(loop.track, s0, v0=v0)
     loop.reset(x0)
     recs = loop.run(ticks)
