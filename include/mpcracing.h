@@ -38,7 +38,8 @@ extern "C" {
    102: mr_inputs.order_hint, dispatch_order 2; 103: mr_tyrefit_config, mr_tyre_loss_grad, mr_tyre_fit; still 103, additions only:
    mr_vehicle_step, mr_tyre_rollout, mr_plant_params_default, mr_plant_step_params, mr_plant_rollout,
    mr_pid_gains_default, mr_pid_control, mr_pid_drive, mr_pid_segment_times, mr_ga_random, mr_ga_breed,
-   mr_solve_batch_horizons, mr_warm, mr_solve_batch_warm, mr_warm_shift) */
+   mr_solve_batch_horizons, mr_warm, mr_solve_batch_warm, mr_warm_shift,
+   mr_mpcseg_runtime, mr_mpcseg_inputs, mr_mpcseg_apply) */
 #define MR_ABI_VERSION 103
 
 #define MR_OK 0
@@ -525,6 +526,48 @@ int mr_ga_breed(int32_t n_island, int32_t P, int32_t K, int32_t D, int32_t pairs
                 const int32_t* col /* HOST, [D] or NULL */, const double* times, double* avg, const double* lo, const double* hi, double kT, double lambda_T, double mutation_rate,
                 uint64_t seed, uint64_t island0, uint64_t generation, double* r, double* best_r, int32_t* best_idx,
                 double* best_genes, void* hip_stream);
+
+/* ---- segment drives of the MPC: the fitness of the weight-tuning GA (csrc/mr_mpcseg.h) --------------------
+ * GA/mpcGA.py tunes the five RuntimeControllerParameters over segments of the lap; its segment time is a random
+ * placeholder (mpcGA.py:43).  Here vehicle i of n = n_ind K drives segment i % K with the runtime vector of
+ * individual i / K, one tick being mr_agent_sense, mr_mpcseg_inputs, mr_solve_batch_horizons (or _warm) and
+ * mr_mpcseg_apply on one stream.  A vehicle whose drive is over (done[i] != 0) gets horizon 0, which the solve
+ * skips, and is not stepped.  All arrays are caller-owned DEVICE pointers; nothing synchronises.
+ * mem [MR_MPCSEG_NMEM][n] = old_yaw, prev_progress (NaN: none yet, as the agent's None), cmd_throttle, cmd_steer,
+ * cmd_brake, travelled_prev; row 1 is the prev_progress argument of mr_agent_sense. */
+#define MR_MPCSEG_NMEM 6
+/* Once per generation: runtime[d][ind K + k] = lo[d] + genes[ind][d] (hi[d] - lo[d]), genes [n_ind][5] in
+   normalised units, lo, hi [5]; d_max not NaN: row 1 is d_max instead (the class attribute that the reference's
+   NLP reads, control/MPC.py:50).  runtime [5][n_ind K] is mr_inputs.runtime. */
+int mr_mpcseg_runtime(int32_t n_ind, int32_t K, const double* genes, const double* lo, const double* hi, double d_max,
+                      double* runtime, void* hip_stream);
+/* Every tick (tick = 0, 1, ...) after mr_agent_sense wrote progress [n] from state [6][n].  Vehicle i with
+   done[i] != 0: horizon_out[i] = 0, nothing else written.  Otherwise, with travelled = mod(progress - s_start, L),
+   minus L above L / 2, and need = mod(s_end - s_start, L) of segment i % K (s_start, s_end [K]): when travelled >=
+   need, times[i] = dt ((tick - 1) + (need - a) / (travelled - a)), a = mem's travelled_prev, inf at tick 0; a
+   non-finite progress gives inf; either way done[i] = 1, ticks_done[i] = tick + 1, horizon_out[i] = 0 and nothing
+   else is written (times and ticks_done of a vehicle that never finishes keep the caller's values).  A vehicle
+   that drives on gets state0 [8][n] = X, Y, yaw, vx, vy, the yaw rate as the wrapped difference of yaw and
+   old_yaw times (1 / dt) (agent.py:240-249 as torch divides by a host scalar on the device; NaN old_yaw: NaN), cmd_brake == 0 ? cmd_throttle : -cmd_brake
+   (agent.py:149), cmd_steer; with U_prev [2][N][n] (and horizon_prev [n] or NULL = N, its horizons Np),
+   u_init[:, k, i] = U_prev[:, min(k + 1, Np - 1), i] (control/MPC.py:120-121; u_init and U_prev both or neither);
+   horizon_out[i] = horizon_in[i], or without horizon_in N, or with hz_lookahead > 0 the reference's speed rule
+   ceil((1 / (Ts max(vx, 1e-3))) hz_lookahead) clamped to [hz_min, N] (script/test_mpc.py:32-33 in the operations
+   of torch's scalar / tensor; NaN speed: 0). */
+int mr_mpcseg_inputs(int32_t n, int32_t K, int32_t N, int32_t tick, double dt, double L, const double* state,
+                     const double* progress, const double* mem, const double* s_start, const double* s_end,
+                     const double* U_prev, const int32_t* horizon_prev, const int32_t* horizon_in,
+                     double hz_lookahead, double Ts, int32_t hz_min, double* state0, double* u_init,
+                     int32_t* horizon_out, int32_t* done, double* times, int32_t* ticks_done, void* hip_stream);
+/* Every tick after the solve.  Vehicle i with done[i] != 0 is left alone (state and mem bitwise).  Otherwise
+   (throttle, steer) = U[:, 0, i] of U [2][N][n], or (0.5, 0.0) with U NULL (agent.py:283); cmd_brake = -throttle
+   and cmd_throttle = 0 for a negative throttle, else 0 and throttle (agent.py:289-306); state [6][n] takes one
+   step of plant `model` (MR_PLANT_*) with the command cmd_throttle - cmd_brake and the parameters params
+   [P][MR_PLANT_NPAR] (P == 1 or n; NULL with P = 0: the defaults) as mr_plant_step_params computes it; mem takes
+   the yaw before the step, this tick's progress, the three commands and this tick's travelled. */
+int mr_mpcseg_apply(int32_t model, int32_t n, int32_t K, int32_t N, double dt, double L, double* state, double* mem,
+                    const double* progress, const double* s_start, const int32_t* done, const double* U, int32_t P,
+                    const double* params, void* hip_stream);
 
 #ifdef __cplusplus
 }

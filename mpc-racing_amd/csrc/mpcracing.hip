@@ -22,6 +22,7 @@
 #include "mr_pid.h"
 #include "mr_ga.h"
 #include "mr_warm.h"
+#include "mr_mpcseg.h"
 #include <vector>
 
 using namespace mr;
@@ -651,6 +652,25 @@ __global__ __launch_bounds__(64) void ga_breed_kernel(GaBreedArgs A) {
   ga_breed_island(w, A, (int)blockIdx.x, &sh);
 }
 
+// The glue of the MPC's segment drives (mr_mpcseg.h): one lane per vehicle, like the other per-tick kernels.
+__global__ __launch_bounds__(kTrackBlock) void mpcseg_runtime_kernel(int n_ind, int K, const double* genes,
+                                                                     const double* lo, const double* hi, double d_max,
+                                                                     double* runtime) {
+  const int j = blockIdx.x * kTrackBlock + threadIdx.x;
+  if (j >= n_ind * K) return;
+  mpcseg_runtime_vehicle(n_ind, K, j, genes, lo, hi, d_max, runtime);
+}
+__global__ __launch_bounds__(kTrackBlock) void mpcseg_inputs_kernel(MpcSegInputsArgs A) {
+  const int i = blockIdx.x * kTrackBlock + threadIdx.x;
+  if (i >= A.n) return;
+  mpcseg_inputs_vehicle(A, i);
+}
+__global__ __launch_bounds__(kTrackBlock) void mpcseg_apply_kernel(MpcSegApplyArgs A) {
+  const int i = blockIdx.x * kTrackBlock + threadIdx.x;
+  if (i >= A.n) return;
+  mpcseg_apply_vehicle(A, i);
+}
+
 // A device-side argument check (mr_tyre_fit, mr_tyre_rollout, mr_plant_rollout): n flags zeroed on the device,
 // launch(flags) enqueues the checking kernels, the flags come back in bad[0..n).  Nothing the kernels test is
 // used as an index before it is known to be in range; the flags are freed on every path.
@@ -1259,6 +1279,58 @@ int mr_ga_breed(int32_t n_island, int32_t P, int32_t K, int32_t D, int32_t pairs
   const GaBreedArgs A = make_ga_breed_args(n_island, P, K, D, pairs, genes, ld, col, times, avg, lo, hi, kT, lambda_T,
                                            mutation_rate, seed, island0, generation, r, best_r, best_idx, best_genes);
   hipLaunchKernelGGL(ga_breed_kernel, dim3((unsigned)n_island), dim3(64), 0, (hipStream_t)hip_stream, A);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_mpcseg_runtime(int32_t n_ind, int32_t K, const double* genes, const double* lo, const double* hi, double d_max,
+                      double* runtime, void* hip_stream) {
+  if (const char* e = mpcseg_runtime_check(n_ind, K)) return fail(MR_ERR_ARG, e);
+  if (!genes || !lo || !hi || !runtime) return fail(MR_ERR_ARG, "null argument");
+  if (n_ind == 0) return MR_OK;
+  int dev = -1;
+  if (pointer_device(runtime, &dev) != 0) return fail(MR_ERR_ARG, "runtime is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  const int n = n_ind * K;
+  hipLaunchKernelGGL(mpcseg_runtime_kernel, dim3((n + kTrackBlock - 1) / kTrackBlock), dim3(kTrackBlock), 0,
+                     (hipStream_t)hip_stream, (int)n_ind, (int)K, genes, lo, hi, d_max, runtime);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_mpcseg_inputs(int32_t n, int32_t K, int32_t N, int32_t tick, double dt, double L, const double* state,
+                     const double* progress, const double* mem, const double* s_start, const double* s_end,
+                     const double* U_prev, const int32_t* horizon_prev, const int32_t* horizon_in,
+                     double hz_lookahead, double Ts, int32_t hz_min, double* state0, double* u_init,
+                     int32_t* horizon_out, int32_t* done, double* times, int32_t* ticks_done, void* hip_stream) {
+  if (const char* e = mpcseg_inputs_check(n, K, N, tick, dt, L, hz_lookahead, Ts, hz_min, horizon_in, U_prev, u_init))
+    return fail(MR_ERR_ARG, e);
+  if (!state || !progress || !mem || !s_start || !s_end || !state0 || !horizon_out || !done || !times || !ticks_done)
+    return fail(MR_ERR_ARG, "null argument");
+  if (n == 0) return MR_OK;
+  int dev = -1;
+  if (pointer_device(state, &dev) != 0) return fail(MR_ERR_ARG, "state is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  const MpcSegInputsArgs A{n, K, N, tick, hz_min, dt, L, hz_lookahead, Ts, state, progress, mem, s_start, s_end,
+                           U_prev, horizon_prev, horizon_in, state0, u_init, horizon_out, done, times, ticks_done};
+  hipLaunchKernelGGL(mpcseg_inputs_kernel, dim3((n + kTrackBlock - 1) / kTrackBlock), dim3(kTrackBlock), 0,
+                     (hipStream_t)hip_stream, A);
+  HIP_TRY(hipGetLastError());
+  return MR_OK;
+}
+
+int mr_mpcseg_apply(int32_t model, int32_t n, int32_t K, int32_t N, double dt, double L, double* state, double* mem,
+                    const double* progress, const double* s_start, const int32_t* done, const double* U, int32_t P,
+                    const double* params, void* hip_stream) {
+  if (const char* e = mpcseg_apply_check(model, n, K, N, dt, L, P, params)) return fail(MR_ERR_ARG, e);
+  if (!state || !mem || !progress || !s_start || !done) return fail(MR_ERR_ARG, "null argument");
+  if (n == 0) return MR_OK;
+  int dev = -1;
+  if (pointer_device(state, &dev) != 0) return fail(MR_ERR_ARG, "state is not a HIP device pointer");
+  MR_GUARD_DEVICE(dev);
+  const MpcSegApplyArgs A{model, n, K, N, P, dt, L, state, mem, progress, s_start, done, U, params};
+  hipLaunchKernelGGL(mpcseg_apply_kernel, dim3((n + kTrackBlock - 1) / kTrackBlock), dim3(kTrackBlock), 0,
+                     (hipStream_t)hip_stream, A);
   HIP_TRY(hipGetLastError());
   return MR_OK;
 }

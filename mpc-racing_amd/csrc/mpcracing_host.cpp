@@ -19,6 +19,7 @@
 #include "mr_ga.h"
 #include "mr_probe.h"
 #include "mr_warm.h"
+#include "mr_mpcseg.h"
 
 using namespace mr;
 
@@ -506,6 +507,38 @@ int mrh_ga_breed(int n_island, int P, int K, int D, int pairs, double* genes, in
     host_wave_call([&](const Wv& w) { ga_breed_island(w, A, i, sh); });
     delete sh;
   }
+  return 0;
+}
+
+// ---- the glue of the MPC's segment drives (mr_mpcseg.h): one lane at a time ----
+int mrh_mpcseg_runtime(int n_ind, int K, const double* genes, const double* lo, const double* hi, double d_max,
+                       double* runtime) {
+  if (const char* e = mpcseg_runtime_check(n_ind, K)) return tyrefit_fail(e);
+  if (!genes || !lo || !hi || !runtime) return tyrefit_fail("null argument");
+  for (int j = 0; j < n_ind * K; ++j) mpcseg_runtime_vehicle(n_ind, K, j, genes, lo, hi, d_max, runtime);
+  return 0;
+}
+int mrh_mpcseg_inputs(int n, int K, int N, int tick, double dt, double L, const double* state, const double* progress,
+                      const double* mem, const double* s_start, const double* s_end, const double* U_prev,
+                      const int32_t* horizon_prev, const int32_t* horizon_in, double hz_lookahead, double Ts,
+                      int hz_min, double* state0, double* u_init, int32_t* horizon_out, int32_t* done, double* times,
+                      int32_t* ticks_done) {
+  if (const char* e = mpcseg_inputs_check(n, K, N, tick, dt, L, hz_lookahead, Ts, hz_min, horizon_in, U_prev, u_init))
+    return tyrefit_fail(e);
+  if (!state || !progress || !mem || !s_start || !s_end || !state0 || !horizon_out || !done || !times || !ticks_done)
+    return tyrefit_fail("null argument");
+  const MpcSegInputsArgs A{n, K, N, tick, hz_min, dt, L, hz_lookahead, Ts, state, progress, mem, s_start, s_end,
+                           U_prev, horizon_prev, horizon_in, state0, u_init, horizon_out, done, times, ticks_done};
+  for (int i = 0; i < n; ++i) mpcseg_inputs_vehicle(A, i);
+  return 0;
+}
+int mrh_mpcseg_apply(int model, int n, int K, int N, double dt, double L, double* state, double* mem,
+                     const double* progress, const double* s_start, const int32_t* done, const double* U, int P,
+                     const double* params) {
+  if (const char* e = mpcseg_apply_check(model, n, K, N, dt, L, P, params)) return tyrefit_fail(e);
+  if (!state || !mem || !progress || !s_start || !done) return tyrefit_fail("null argument");
+  const MpcSegApplyArgs A{model, n, K, N, P, dt, L, state, mem, progress, s_start, done, U, params};
+  for (int i = 0; i < n; ++i) mpcseg_apply_vehicle(A, i);
   return 0;
 }
 

@@ -16,6 +16,7 @@ MR_PLANT = {"kin": 0, "dyn": 1, "blend": 2}
 MR_PLANT_NPAR = 22  # include/mpcracing.h
 MR_PID_NGAIN, MR_PID_NMEM, MR_PID_NOUT, MR_PID_NLOG = 8, 4, 8, 14  # include/mpcracing.h
 MR_GA_P_MAX, MR_GA_K_MAX, MR_GA_D_MAX = 64, 64, 16  # csrc/mr_ga.h
+MR_MPCSEG_NMEM = 6  # include/mpcracing.h
 MR_OPT = {"sgd": 0, "adam": 1, "adamw": 2}
 STATUS = {0: "solved", 1: "acceptable", 2: "max_iter", 3: "failed", 4: "infeasible"}
 
@@ -69,7 +70,8 @@ EXPORTS = ["mr_version", "mr_last_error", "mr_config_default", "mr_create", "mr_
            "mr_tyrefit_config_default", "mr_tyre_loss_grad", "mr_tyre_fit", "mr_vehicle_step", "mr_tyre_rollout",
            "mr_plant_params_default", "mr_plant_step_params", "mr_plant_rollout",
            "mr_pid_gains_default", "mr_pid_control", "mr_pid_drive", "mr_pid_segment_times", "mr_ga_random",
-           "mr_ga_breed", "mr_solve_batch_horizons", "mr_solve_batch_warm", "mr_warm_shift"]
+           "mr_ga_breed", "mr_solve_batch_horizons", "mr_solve_batch_warm", "mr_warm_shift",
+           "mr_mpcseg_runtime", "mr_mpcseg_inputs", "mr_mpcseg_apply"]
 
 
 def _bind_product(lib):
@@ -119,6 +121,9 @@ def _bind_product(lib):
     lib.mr_pid_segment_times.argtypes = [V, _I32, _I32, _I32, _I32, _D, V, V, V, V, _I32, V, V, V, V]
     lib.mr_ga_random.argtypes = [_U64, _U64, _U64, _U64, ctypes.c_int64, V]
     lib.mr_ga_breed.argtypes = [_I32] * 5 + [V, _I32, _PI32] + [V] * 4 + [_D] * 3 + [_U64] * 3 + [V] * 5
+    lib.mr_mpcseg_runtime.argtypes = [_I32, _I32, V, V, V, _D, V, V]
+    lib.mr_mpcseg_inputs.argtypes = [_I32] * 4 + [_D, _D] + [V] * 8 + [_D, _D, _I32] + [V] * 7
+    lib.mr_mpcseg_apply.argtypes = [_I32] * 4 + [_D, _D] + [V] * 6 + [_I32, V, V]
     return lib
 
 
@@ -216,6 +221,9 @@ def load_host_twin(path=HOST_TWIN_LIB):
     lib.mrh_pid_segment_times.argtypes = [V, I, _D, I, I, I, I, I, _D, V, V, V, V, I, V, V, V, I]
     lib.mrh_ga_random.argtypes = [_U64, _U64, _U64, _U64, ctypes.c_int64, V]
     lib.mrh_ga_breed.argtypes = [I] * 5 + [V, I, _PI32] + [V] * 4 + [_D] * 3 + [_U64] * 3 + [V] * 4
+    lib.mrh_mpcseg_runtime.argtypes = [I, I, V, V, V, _D, V]
+    lib.mrh_mpcseg_inputs.argtypes = [I] * 4 + [_D, _D] + [V] * 8 + [_D, _D, I] + [V] * 6
+    lib.mrh_mpcseg_apply.argtypes = [I] * 4 + [_D, _D] + [V] * 6 + [I, V]
     lib.mrh_pacejka_dparams.argtypes = [_PD, _D, _D, _PD, _PD]
     lib.mrh_probe_layout.argtypes = [_PI32]
     lib.mrh_probe_layout.restype = None

@@ -11,7 +11,7 @@ import subprocess
 from .abi import CSRC, PRODUCT_LIB, PROBE_LIB, HOST_TWIN_LIB
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["mpcracing.hip", "mr_batch.h", "mr_solver.h", "mr_common.h", "gen_dynamics.h", "mr_wave.h", "mr_wave_prims.h", "mr_track.h", "mr_agent.h", "mr_plant.h", "mr_tyrefit.h", "mr_rollout.h", "mr_plantroll.h", "mr_pid.h", "mr_ga.h", "mr_warm.h"]
+SOURCES = ["mpcracing.hip", "mr_batch.h", "mr_solver.h", "mr_common.h", "gen_dynamics.h", "mr_wave.h", "mr_wave_prims.h", "mr_track.h", "mr_agent.h", "mr_plant.h", "mr_tyrefit.h", "mr_rollout.h", "mr_plantroll.h", "mr_pid.h", "mr_ga.h", "mr_warm.h", "mr_mpcseg.h"]
 PROBE_SOURCES = ["mr_probe.hip", "mr_probe.h", "mr_batch.h", "mr_solver.h", "mr_common.h", "gen_dynamics.h", "mr_wave.h",
                  "mr_wave_prims.h"]
 INCLUDE = os.path.abspath(os.path.join(CSRC, "..", "..", "include"))
